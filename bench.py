@@ -10,8 +10,15 @@ A "step" is one full product C = A*B over GF(2) with A and B already resident in
 does  broadcast(B)  ->  local product of the row block  ->  gather(C blocks) on rank 0.
 
 Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP-event timed on its own
-stream inside the library) and `cpu_baseline` (the oracle's single-thread M4RM+Strassen port on
-a bounded sample, N = 1 only).
+stream inside the library).  A plain run does nothing else: set-up, warm-up, the timed steps,
+the line.  `--full` adds the rest, each after the timed steps except the first: `cpu_baseline`
+(the oracle's single-thread M4RM+Strassen port on a bounded sample, N = 1 only, run before the
+GPU loop), the sha256 parity of the last product, the other BASELINE configurations, the
+elimination leg and the host-path leg.
+
+`--dump-outputs DIR` writes what the last timed step computed (C = A*B) as float32 .npy files:
+every bit of a fixed, seeded sample of C's rows, and the parity of every row and every column
+of C (so that a wrong bit anywhere in C changes the dump).
 """
 import argparse
 import json
@@ -335,6 +342,55 @@ def _elimination(device, torch, sizes=(4096, 65536)):
     return out
 
 
+def _xor_fold(t, dim):
+    """XOR of a 2-D int64 tensor along `dim` by pairwise halving on the device; `dim` is kept, with size 1."""
+    import torch
+    while t.shape[dim] > 1:
+        if t.shape[dim] % 2:
+            t = torch.cat([t, torch.zeros_like(t.narrow(dim, 0, 1))], dim)
+        h = t.shape[dim] // 2
+        t = t.narrow(dim, 0, h) ^ t.narrow(dim, h, h)
+    return t
+
+
+def _parity64(x):
+    """Parity of every int64 word of `x` (0 / 1).  The shifts are arithmetic, but sign copies only reach bits above the ones that
+    are folded into bit 0."""
+    for s in (32, 16, 8, 4, 2, 1):
+        x = x ^ (x >> s)
+    return x & 1
+
+
+def _dump_outputs(directory, panels, n, budget_bytes=32 << 20):
+    """Writes C (n x n bits, given as column panels: 2-D int64 tensors whose rows, concatenated panel after panel, are the rows of
+    C in the M4RI layout) to `directory` as float32 .npy files, 0.0 / 1.0 per bit:
+      C_sample_rows.npy       every bit of a fixed sample of rows (seed 20261015, as many rows as `budget_bytes` holds, sorted)
+      C_sample_row_index.npy  which rows those are
+      C_row_parity.npy        XOR of the bits of every row of C
+      C_col_parity.npy        XOR of the bits of every column of C
+    (C_sample_row_index is float64, the rest float32; about budget_bytes + 8 n bytes in all)."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    k = max(1, min(n, budget_bytes // (4 * n)))
+    idx = np.sort(np.random.default_rng(20261015).choice(n, size=k, replace=False))
+    idx_t = torch.from_numpy(idx).to(panels[0].device)
+
+    def bits(words):  # (r, w) uint64 -> (r, 64 w) float32, bit j of a row = word j // 64, bit j % 64
+        return np.unpackbits(words.view(np.uint8).reshape(words.shape[0], -1), axis=1, bitorder="little").astype(np.float32)
+
+    rows = np.concatenate([p[idx_t].cpu().numpy().view(np.uint64) for p in panels], axis=1)
+    cols = np.concatenate([_xor_fold(p, 0).cpu().numpy().view(np.uint64) for p in panels], axis=1)
+    row_x = _xor_fold(panels[0], 1)
+    for p in panels[1:]:
+        row_x = row_x ^ _xor_fold(p, 1)
+    out = {"C_sample_rows": bits(rows)[:, :n], "C_sample_row_index": idx.astype(np.float64),
+           "C_row_parity": _parity64(row_x[:, 0]).cpu().numpy().astype(np.float32), "C_col_parity": bits(cols)[0, :n]}
+    for name, arr in out.items():
+        np.save(os.path.join(directory, name + ".npy"), arr)
+    return {name: list(arr.shape) for name, arr in out.items()}
+
+
 def _sharded_self_check(device, sharded, torch, Bp, Cfull_t, n, nblocks, stream):
     """Cheap default check of a multi-GPU step (rank 0): eight consecutive rows out of every ROW BLOCK of the grid (at least 32
     rows in all, offsets from a fixed seed) are re-multiplied by rank 0 alone from the seeded generator, against every (sub-)panel
@@ -395,7 +451,16 @@ def main():
     ap.add_argument("--density", default="half", choices=["half", "sparse", "ones"],
                     help="N = 1 only: bit density of the synthetic operands -- half = i.i.d. Bernoulli(1/2) (the metric's "
                          "workload), sparse = 1/64, ones = all ones (clock / data-dependence sanity runs, SURVEY.md section 8d)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also run the legs beyond the headline (cpu_baseline, sha256 parity of the last product, configs, "
+                         "elimination, host_path; each --no-* option still skips its leg).  Off: set-up, warm-up, the timed steps, "
+                         "--dump-outputs and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (float32 bits: a fixed, seeded sample of C's rows, "
+                         "the parity of every row and column of C)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: start the N ranks ourselves as fresh child processes (torch.distributed.run, one
@@ -422,14 +487,17 @@ def main():
             os.environ.setdefault("MASTER_PORT", "29541")
         dist.init_process_group(args.backend, rank=rank, world_size=world)
 
-    import __graft_entry__ as ge
-    if rank == 0:
+    # the library build() made is used as it is: building again relinks it, which fails where the tree is not the bench user's to
+    # write.  Only a checkout that has never been built is built here; a library that will not load still fails loudly below
+    if rank == 0 and not os.path.exists(os.path.join(ROOT, "m4ri-rust_amd", "lib", "libm4ri_hip.so")):
+        import __graft_entry__ as ge
         ge.build()
     if multi:
         dist.barrier()
     import m4ri_rust_amd  # noqa: F401
     from m4ri_rust_amd import device
     from m4ri_rust_amd import sharded
+    device._lib.lib()  # loads the shared object and resolves every declared symbol (raises if it is missing or broken)
 
     n = args.n
     assert n % (64 * world) == 0
@@ -573,10 +641,10 @@ def main():
         else:
             device.mul(A, B, C=C, algo=args.algo, param=args.levels, stream=stream)
 
-    # the CPU baseline leg first (N = 1 only): the timed GPU loop then ends the run, so a driver-side utilisation sample
-    # taken near the end sees the GPU busy
+    # the CPU baseline leg first (N = 1, --full or --check): the timed GPU loop then ends the run, so a driver-side utilisation
+    # sample taken near the end sees the GPU busy
     cpu_baseline, cpu_sample = (None, None)
-    if not multi and not args.no_cpu:
+    if not multi and not args.no_cpu and (args.full or args.check):
         cpu_baseline, cpu_sample = _cpu_baseline(args)
         if not args.check:
             cpu_sample = None
@@ -636,8 +704,11 @@ def main():
     if multi and not args.no_parity:
         self_check = _sharded_self_check(device, sharded, torch, [device.DMat.from_torch(b_src_t[j_][p_], ncp) for j_ in range(Q) for p_ in range(P)],
                                          [Cfull_t[j_][p_] for j_ in range(Q) for p_ in range(P)], n, R, stream)
+    dumped = None
+    if args.dump_outputs:  # before the --full legs: the host-path leg frees C
+        dumped = _dump_outputs(args.dump_outputs, [C_t] if not multi else [Cfull_t[j_][p_] for j_ in range(Q) for p_ in range(P)], n)
     parity = None
-    if not multi and not args.no_parity and args.density == "half":
+    if not multi and args.full and not args.no_parity and args.density == "half":
         want = _golden_digests().get("sq_%d" % n, {}).get("sha256_c")
         if want:
             parity = _sha256_of(C, stream) == want  # the product of the LAST timed step
@@ -781,11 +852,13 @@ def main():
             Ad, Bd = device.DMat.random(cn, cn, 1), device.DMat.random(cn, cn, 2)
             out["cpu_baseline"]["gpu_matches_cpu_sample"] = bool(
                 np.array_equal(device.mul(Ad, Bd, algo=args.algo, param=args.levels).to_words(), cpu_sample))
-    if not multi and not args.no_configs and args.density == "half":
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if not multi and args.full and not args.no_configs and args.density == "half":
         out["configs"] = _extra_configs(device, torch, stream)
-    if not multi and not args.no_elim and args.density == "half":
+    if not multi and args.full and not args.no_elim and args.density == "half":
         out["elimination"] = _elimination(device, torch)
-    if not multi and not args.no_host_path and args.density == "half":
+    if not multi and args.full and not args.no_host_path and args.density == "half":
         del A, B, C, A_t, B_t, C_t  # the resident operands and (gf2_trim) the 15 GiB arena go back first
         torch.cuda.empty_cache()
         device._lib.lib().gf2_trim()

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r03f
 mkdir -p $O
 cd $R
-python3 bench.py --steps 20 --warmup 5 > $O/final_bench.json 2> $O/final_bench.err
+python3 bench.py --steps 20 --warmup 5 --full > $O/final_bench.json 2> $O/final_bench.err
 echo "bench done"
 python3 tools/lpn_bench.py --json > $O/lpn_cold_warm.jsonl 2>/dev/null
 tools/bench_shapes > $O/bench_shapes.jsonl 2>/dev/null

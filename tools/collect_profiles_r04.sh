@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r04f
 mkdir -p $O
 cd $R
-python3 bench.py --steps 20 --warmup 5 > $O/final_bench.json 2> $O/final_bench.err
+python3 bench.py --steps 20 --warmup 5 --full > $O/final_bench.json 2> $O/final_bench.err
 echo "bench done"
 python3 tools/lpn_bench.py --json 2>/dev/null | grep "^{" > $O/lpn_cold_warm.jsonl
 CONFIGS_LPN_ONLY=1 CONFIGS_LPN_V=1,64,128,256 python3 tools/configs_only.py 2>/dev/null | grep "^config" > $O/lpn_bench_leg.txt

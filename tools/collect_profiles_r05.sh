@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r05f
 mkdir -p $O
 cd $R
-python3 bench.py --steps 20 --warmup 5 > $O/final_bench.json 2> $O/final_bench.err
+python3 bench.py --steps 20 --warmup 5 --full > $O/final_bench.json 2> $O/final_bench.err
 echo "bench done"
 python3 tools/av_breakdown.py 2>/dev/null | grep -v amdgpu > $O/av_breakdown.txt
 python3 tools/host_plan_ab.py 32768 65536 16384 2>/dev/null | grep -v amdgpu > $O/host_plan_ab.txt
