@@ -6,7 +6,8 @@
  * in `extern "C"` blocks and that the friendly layer (BinMatrix / BinVector) calls.  Every
  * declaration cites the reference interface it replaces (paths relative to the reference
  * repository root).  Host code that links m4ri-sys against this library instead of libm4ri.a
- * needs no source change: see INTEGRATION.md.
+ * needs no source change: see INTEGRATION.md.  (The result side copy, gf2_set_result_side_cols, is
+ * opt-in and off by default: it asks the caller to report stores through rows[].)
  *
  * Section 2 is the device-resident API (raw device pointers, explicit HIP stream) used by
  * bench.py, the multi-GPU host layer and callers that chain products without the PCIe round
@@ -236,6 +237,13 @@ mzd_t *gf2_mul_multi(mzd_t *C, mzd_t const *A, mzd_t const *B, int algo, int par
  * drop the copy themselves: the cache is keyed by the block that M and its windows share. */
 int gf2_mzd_cache_on_device(mzd_t const *M);
 void gf2_mzd_uncache(mzd_t const *M);
+
+/* Result side copy (opt-in): a product into a NULL destination with at most `cols` columns (and at least 1 MiB
+ * of rows) also keeps its packed transposed form on the host, and mzd_transpose of that product is served from it.  Stores through
+ * rows[] are invisible to the library, so a caller that opts in must call gf2_mzd_uncache(C) after storing into such a product;
+ * without that, mzd_transpose returns the bits of the product as it was computed.  0 = off: the default, unless the environment
+ * sets M4RI_HIP_RESULT_SIDE_COLS.  Returns the previous value; takes effect for products that start after the call. */
+int gf2_set_result_side_cols(int cols);
 
 /* Host blocks of at least M4RI_HIP_PIN_MIN_BYTES (1 MiB) are pinned so that uploads and downloads run at the PCIe rate; pinning
  * fresh pages costs about 100 ms per 512 MiB, so freed blocks are pooled (up to M4RI_HIP_PIN_CACHE_BYTES, 8 GiB).  A caller that

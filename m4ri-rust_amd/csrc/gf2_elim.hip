@@ -981,13 +981,18 @@ __global__ __launch_bounds__(256) void gf2_scatter_rows_kernel(u64 *__restrict__
   for (int w = threadIdx.x; w < words; w += 256) X[d * ldx + w] = R[(long long)k * ldr + w];
 }
 
-// flag = 1 if any word of rows [row_lo, rows) x words [0, words) is non-zero
+// flag = 1 if any bit of rows [row_lo, rows) x columns [0, cols) is non-zero.  The bits past cols in the last word are not looked at:
+// mzd_solve_left's right-hand side B is copied in whole words, and a window of B shares its last word with its parent.
 __global__ __launch_bounds__(256) void gf2_any_nonzero_kernel(const u64 *__restrict__ M, long long ld, int row_lo, int rows,
-                                                              int words, int *flag) {
+                                                              int cols, int *flag) {
+  const int words = (cols + 63) >> 6;
+  const u64 maskL = (cols & 63) ? ((1ull << (cols & 63)) - 1) : ~0ull;
   const long long total = (long long)(rows - row_lo) * words;
   bool nz = false;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256)
-    nz |= M[(row_lo + i / words) * ld + i % words] != 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const int w = (int)(i % words);
+    nz |= (M[(row_lo + i / words) * ld + w] & (w == words - 1 ? maskL : ~0ull)) != 0;
+  }
   if (__ballot(nz) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
 }
 
@@ -1139,11 +1144,11 @@ extern "C" hipError_t gf2k_scatter_rows(u64 *X, long long ldx, const u64 *R, lon
   return hipGetLastError();
 }
 
-extern "C" hipError_t gf2k_any_nonzero(const u64 *M, long long ld, int row_lo, int rows, int words, int *flag, hipStream_t s) {
-  if (rows <= row_lo || words <= 0) return hipSuccess;
-  long long total = (long long)(rows - row_lo) * words;
+extern "C" hipError_t gf2k_any_nonzero(const u64 *M, long long ld, int row_lo, int rows, int cols, int *flag, hipStream_t s) {
+  if (rows <= row_lo || cols <= 0) return hipSuccess;
+  long long total = (long long)(rows - row_lo) * ((cols + 63) / 64);
   long long grid = (total + 255) / 256;
   if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(gf2_any_nonzero_kernel, dim3((unsigned)grid), dim3(256), 0, s, M, ld, row_lo, rows, words, flag);
+  hipLaunchKernelGGL(gf2_any_nonzero_kernel, dim3((unsigned)grid), dim3(256), 0, s, M, ld, row_lo, rows, cols, flag);
   return hipGetLastError();
 }

@@ -74,7 +74,7 @@ hipError_t gf2k_elim_small(uint64_t *A, long long lda, int m, int ncols, int lim
 hipError_t gf2k_set_diag(uint64_t *M, long long ld, int n, long long col0, hipStream_t s);
 hipError_t gf2k_scatter_rows(uint64_t *X, long long ldx, const uint64_t *R, long long ldr, int words, const int *pivcols,
                              int rank, hipStream_t s);
-hipError_t gf2k_any_nonzero(const uint64_t *M, long long ld, int row_lo, int rows, int words, int *flag, hipStream_t s);
+hipError_t gf2k_any_nonzero(const uint64_t *M, long long ld, int row_lo, int rows, int cols, int *flag, hipStream_t s);
 int gf2k_m4rm_rows_per_tile(int cfg);
 // 64-bit words of partial-tile scratch a stream-K launch of variant `cfg` with `nseg` segments needs (two slots per segment)
 long long gf2k_m4rm_streamk_words(int cfg, int nseg);
@@ -110,7 +110,7 @@ hipError_t gf2k_va(const uint64_t *A, long long lda, const uint64_t *B, long lon
 hipError_t gf2k_xor2d(uint64_t *C, long long ldc, const uint64_t *A, long long lda, const uint64_t *B, long long ldb,
                       int rows, int words, hipStream_t stream);
 hipError_t gf2k_padcopy(uint64_t *dst, long long ldd, int drows, int dwords, const uint64_t *src, long long lds_, int srows,
-                        int swords, hipStream_t stream);
+                        int scols, hipStream_t stream);  // scols: the source's columns (its last word is masked)
 hipError_t gf2k_fill_random(uint64_t *M, long long ld, int rows, int cols, uint64_t seed, long long row0, long long fullw,
                             long long colw0, hipStream_t stream);
 hipError_t gf2k_diff(const uint64_t *A, long long lda, const uint64_t *B, long long ldb, int rows, int cols, int *diff,

@@ -2390,11 +2390,15 @@ __global__ __launch_bounds__(256) void gf2_xor2d_kernel(u64 *__restrict__ C, lon
 
 // dst (drows x dwords words, dense) = src (srows x swords) in its top left corner, zeros elsewhere: operands padded up to
 // dimensions that divide by the Strassen level plan (m4ri_hip_api.cpp, mul_strassen_padded)
-// dst (drows x dwords, zero padded) <- src (srows x swords); 16-byte accesses where both rows allow them (ldd, lds_ even and
+// dst (drows x dwords, zero padded) <- src (srows x scols bits); 16-byte accesses where both rows allow them (ldd, lds_ even and
 // 16-byte aligned bases: `vec`), one block row per blockIdx.y step (no division in the loop)
+// The source's last word is masked to its `scols` columns: a window whose column end is not a multiple of 64 shares that word with
+// its parent, and bits past the operand in the padded copy would turn into bits of C past n (the corner is copied in whole words).
 __global__ __launch_bounds__(256) void gf2_padcopy_kernel(u64 *__restrict__ dst, long long ldd, int drows, int dwords,
-                                                          const u64 *__restrict__ src, long long lds_, int srows, int swords, int vec) {
+                                                          const u64 *__restrict__ src, long long lds_, int srows, int scols, int vec) {
   const int pairs = (dwords + 1) >> 1;
+  const int swords = (scols + 63) >> 6;
+  const u64 maskS = (scols & 63) ? ((1ull << (scols & 63)) - 1) : ~0ull;
   for (int r = blockIdx.y; r < drows; r += gridDim.y) {
     u64 *d = dst + (long long)r * ldd;
     const u64 *sr = src + (long long)r * lds_;
@@ -2410,6 +2414,8 @@ __global__ __launch_bounds__(256) void gf2_padcopy_kernel(u64 *__restrict__ dst,
         if (w < swords) v0 = sr[w];
         if (w + 1 < swords) v1 = sr[w + 1];
       }
+      if (w == swords - 1) v0 &= maskS;
+      if (w + 1 == swords - 1) v1 &= maskS;
       if (w + 1 < dwords && vec) {
         *reinterpret_cast<uint4 *>(d + w) = make_uint4((u32)v0, (u32)(v0 >> 32), (u32)v1, (u32)(v1 >> 32));
       } else {
@@ -3358,6 +3364,8 @@ static hipError_t tallskinny_impl(const u64 *A, long long lda, const u64 *B, lon
   // few rows a batch of 4096 per workgroup leaves most of the chip idle (65536 x 256 x 256: 14.5 us with RPT = 8, 5.4 with 1).
   // M4RI_HIP_LPN=0 restores the round-2/3 kernels (A/B runs).
   static const int lpn = GF2K_DEV_ENV("M4RI_HIP_LPN", 1);
+  // only gf2_lpnvec_kernel packs `side`: any other kernel would leave it unwritten while the call reports success
+  if (side && (l > 256 || old_only || !lpn)) return hipErrorNotSupported;
   if (l <= 256 && !old_only && lpn) {
     const bool a16 = (lda & 1) == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0;
     const bool c16 = nw == 1 || ((ldc & 1) == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0);
@@ -3396,6 +3404,7 @@ static hipError_t tallskinny_impl(const u64 *A, long long lda, const u64 *B, lon
 #undef GF2_LPNVEC_GO
       return hipGetLastError();
     }
+    if (side) return hipErrorNotSupported;
     const int target = nw == 1 ? 512 : 256;  // workgroups wanted
     int rpt = nw == 1 ? 4 : 8;
     while (rpt > 1 && ((long long)m + 512LL * rpt - 1) / (512LL * rpt) < target) rpt >>= 1;
@@ -3602,12 +3611,12 @@ extern "C" hipError_t gf2k_xor2d(u64 *C, long long ldc, const u64 *A, long long 
 }
 
 extern "C" hipError_t gf2k_padcopy(u64 *dst, long long ldd, int drows, int dwords, const u64 *src, long long lds_, int srows,
-                                   int swords, hipStream_t stream) {
+                                   int scols, hipStream_t stream) {
   if (drows <= 0 || dwords <= 0) return hipSuccess;
   const int vec = !((ldd | lds_) & 1) && !(((uintptr_t)dst | (uintptr_t)src) & 15);
   const int pairs = (dwords + 1) >> 1;
   const unsigned gx = (unsigned)std::min(8, (pairs + 255) / 256), gy = (unsigned)std::min(drows, 65535);
-  hipLaunchKernelGGL(gf2_padcopy_kernel, dim3(gx, gy), dim3(256), 0, stream, dst, ldd, drows, dwords, src, lds_, srows, swords, vec);
+  hipLaunchKernelGGL(gf2_padcopy_kernel, dim3(gx, gy), dim3(256), 0, stream, dst, ldd, drows, dwords, src, lds_, srows, scols, vec);
   return hipGetLastError();
 }
 

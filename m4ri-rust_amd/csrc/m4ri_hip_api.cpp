@@ -1466,8 +1466,8 @@ static int mul_strassen_padded(gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B
   void *ws = nullptr;
   if (int rc = stream_workspace(s, (wordsA + wordsB + wordsC) * sizeof(u64), &ws, 3)) return rc;
   u64 *pa = static_cast<u64 *>(ws), *pb = pa + wordsA, *pc = pb + wordsB;
-  HIP_TRY(gf2k_padcopy(pa, wa, pp.mp, (int)wa, A->data, A->ld, m, words_of(l), s));
-  HIP_TRY(gf2k_padcopy(pb, wb, pp.lp, (int)wb, B->data, B->ld, l, words_of(n), s));
+  HIP_TRY(gf2k_padcopy(pa, wa, pp.mp, (int)wa, A->data, A->ld, m, l, s));
+  HIP_TRY(gf2k_padcopy(pb, wb, pp.lp, (int)wb, B->data, B->ld, l, n, s));
   gf2_dmat Ap{pa, wa, pp.mp, pp.lp}, Bp{pb, wb, pp.lp, pp.np}, Cp{pc, wb, pp.mp, pp.np};
   if (int rc = mul_strassen(&Cp, &Ap, &Bp, 0, pp.L, s, false)) return rc;
   // rows / columns past the operands are zero in the padded product, so whole words of the corner are exact
@@ -1974,16 +1974,24 @@ std::map<const void *, std::shared_ptr<CachedOperand>> g_cache;
 // register file anyway: a product into a library-allocated (NULL) destination with at most M4RI_HIP_RESULT_SIDE_COLS columns also
 // transposes C on the device (one launch) and brings the n x m form down beside C; mzd_transpose of that matrix is then a copy.
 // Keyed like the operand cache by the matrix' block and dropped by the same gf2_cache_forget calls (every library routine that
-// writes a matrix, and mzd_free); stores through rows[] are invisible to the library, as for the operand cache.
+// writes a matrix, and mzd_free).  Stores through rows[] are invisible to the library, as for the operand cache: a caller that
+// makes them (m4ri-sys's mzd_write_bit, BinMatrix::set_window) would read the old bits back from mzd_transpose.  So the side copy
+// is OPT-IN (M4RI_HIP_RESULT_SIDE_COLS or gf2_set_result_side_cols; default 0 = off), for callers that promise gf2_mzd_uncache
+// after such stores.
 struct ResultSide {
   word *buf = nullptr;  // pinned; ncols rows of ld words
   size_t bytes = 0;
   size_t ld = 0;
   int nrows = 0, ncols = 0, rowstride = 0;  // of the product
   const word *row0 = nullptr;
+  bool written = false;  // set by the paths that fill buf; a schedule that ignores the side copy leaves it unregistered
   ~ResultSide() { gf2_pinned_free(buf, bytes); }
 };
 std::map<const void *, std::shared_ptr<ResultSide>> g_result_side;
+std::atomic<int> &result_side_cols() {
+  static std::atomic<int> cols{env_int("M4RI_HIP_RESULT_SIDE_COLS", 0)};
+  return cols;
+}
 
 struct DMatOwner {
   gf2_dmat d{};
@@ -2187,7 +2195,9 @@ HostPlan plan_host_product(int rows, int l, int n, int algo, int param, bool b_r
 // 2^20 x 1): no scratch and no second download queued behind C's on the copy engine.  Complete once stream s has been synchronised.
 int result_side_rows(ResultSide *side, const gf2_dmat &c, int r0, hipStream_t s) {
   const hipError_t e = gf2k_transpose(reinterpret_cast<u64 *>(side->buf) + r0 / 64, (long long)side->ld, c.data, c.ld, c.nrows, c.ncols, s);
-  return e == hipSuccess ? 0 : fail(e, "gf2k_transpose");
+  if (e != hipSuccess) return fail(e, "gf2k_transpose");
+  side->written = true;
+  return 0;
 }
 
 // One to four vectors against many rows of 65..256 bits: the table-free kernel packs the side copy itself (a ballot per vector and 64
@@ -2197,7 +2207,9 @@ int thin_product_with_side(ResultSide *side, u64 *c, long long ldc, const u64 *a
   if (!side || !thin_vector_shape(m, l, b.ncols)) return 0;
   const hipError_t e = gf2k_tallskinny_side(a, lda, b.data, b.ld, c, ldc, m, l, b.ncols, reinterpret_cast<u64 *>(side->buf), (long long)side->ld, s);
   if (e == hipErrorNotSupported) return 0;
-  return e == hipSuccess ? 1 : fail(e, "gf2k_tallskinny_side");
+  if (e != hipSuccess) return fail(e, "gf2k_tallskinny_side");
+  side->written = true;
+  return 1;
 }
 
 // One device's share of a host product: C[r0:r1, :] (+)= A[r0:r1, :] * B on the CURRENT device, stream s.  Four ways to run it,
@@ -2639,8 +2651,8 @@ mzd_t *host_mul_on(mzd_t *C, const mzd_t *A, const mzd_t *B, int accumulate, int
       if (allocated) mzd_free(C);
       return bail("stream");
     }
-    // a fresh thin product also comes back in its packed transposed form (see ResultSide)
-    static const int side_cols = env_int("M4RI_HIP_RESULT_SIDE_COLS", 8);
+    // opted in: a fresh thin product also comes back in its packed transposed form (see ResultSide)
+    const int side_cols = result_side_cols().load(std::memory_order_relaxed);
     std::shared_ptr<ResultSide> side;
     if (allocated && !windows && C->ncols <= side_cols && C->blocks && C->blocks[0].size >= ((size_t)1 << 20)) {
       side = std::make_shared<ResultSide>();
@@ -2651,7 +2663,7 @@ mzd_t *host_mul_on(mzd_t *C, const mzd_t *A, const mzd_t *B, int accumulate, int
     }
     rc = host_mul_range(C, A, B, 0, A->nrows, accumulate, algo, param, s, side.get());
     if (want >= 0) (void)hipSetDevice(cur);
-    if (!rc && side) {
+    if (!rc && side && side->written) {  // (the slab schedule does not write it)
       side->nrows = C->nrows;
       side->ncols = C->ncols;
       side->rowstride = C->rowstride;
@@ -2682,6 +2694,8 @@ extern "C" mzd_t *gf2_mul_multi(mzd_t *C, mzd_t const *A, mzd_t const *B, int al
   }
   return host_mul_on(C, A, B, 0, algo, param, "gf2_mul_multi", devices, ndev);
 }
+
+extern "C" int gf2_set_result_side_cols(int cols) { return result_side_cols().exchange(cols > 0 ? cols : 0); }
 
 void gf2_cache_forget(mzd_t const *M) {
   std::shared_ptr<CachedOperand> c;
@@ -3237,7 +3251,7 @@ extern "C" int mzd_solve_left(mzd_t *A, mzd_t *B, int cutoff, int inconsistency_
     if (inconsistency_check && rank < m) {
       if ((rc = flag.alloc(sizeof(int)))) break;
       e = hipMemsetAsync(flag.p, 0, sizeof(int), s);
-      if (e == hipSuccess) e = gf2k_any_nonzero(T.data + nw, T.ld, rank, m, bw, flag.as<int>(), s);
+      if (e == hipSuccess) e = gf2k_any_nonzero(T.data + nw, T.ld, rank, m, kb, flag.as<int>(), s);  // B's kb columns only
       if (e == hipSuccess) e = hipMemcpyAsync(&inconsistent, flag.p, sizeof(int), hipMemcpyDeviceToHost, s);
       if (e == hipSuccess) e = hipStreamSynchronize(s);
       if (e != hipSuccess) {

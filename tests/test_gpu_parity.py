@@ -1126,8 +1126,18 @@ def test_result_side_copy(pkg, m, n):
     mzd_transpose of that product is served from it and must equal the transposition of the bits the product holds -- for the
     pipelined (A uploaded in row blocks) and the plain (A cached) schedule, ragged row counts included -- and every library call
     that writes the product (mzd_add, mzd_row_swap, a product through a window of it, mzd_copy into it) drops the side copy.
-    Stores through rows[] are invisible to the library: INTEGRATION.md 4d says gf2_mzd_uncache after them, checked here too."""
+    Stores through rows[] are invisible to the library: INTEGRATION.md 4d says gf2_mzd_uncache after them, checked here too.
+    The side copy is opt-in (default off): switched on here with gf2_set_result_side_cols, in this process, so that its kernels (the
+    fused product + side launch, the zero-copy route of a pinned A) count in the launch census like every other kernel."""
     L = pkg._lib.lib()
+    prev = L.gf2_set_result_side_cols(8)
+    try:
+        _result_side_copy_opted_in(pkg, L, m, n)
+    finally:
+        L.gf2_set_result_side_cols(prev)
+
+
+def _result_side_copy_opted_in(pkg, L, m, n):
     l = 256
     a, x = g.random_words(m, l, 3), g.random_words(l, n, 4)
     A, X = pkg.BinMatrix.from_words(a, l), pkg.BinMatrix.from_words(x, n)
@@ -1260,8 +1270,7 @@ def test_mul_nt_every_row_width(dev, l, n):
 
 
 def test_result_side_copy_can_be_switched_off(pkg):
-    """M4RI_HIP_RESULT_SIDE_COLS=0 (the escape hatch for bindings that let users store into any matrix through
-    rows[]): no product carries a side copy, so even a store through rows[] WITHOUT gf2_mzd_uncache is seen by the next
+    """M4RI_HIP_RESULT_SIDE_COLS=0 (the default since the side copy became opt-in; set explicitly here): no product carries a side copy, so even a store through rows[] WITHOUT gf2_mzd_uncache is seen by the next
     mzd_transpose -- and the operator still gives the right bits, A uploaded or cached.  In a child process: the variable is read once."""
     import subprocess
     import sys
@@ -1289,6 +1298,15 @@ def test_lpn_operator_from_several_host_threads(pkg):
     A (uploaded per call: the zero-copy vector kernel; then cached on the device), every thread its own vectors --, so the side copies,
     the pooled pinned blocks with their row-pointer arrays and the per-thread streams are exercised concurrently; every result is
     checked against the oracle."""
+    L = pkg._lib.lib()
+    prev = L.gf2_set_result_side_cols(8)  # the side copies opted in (INTEGRATION.md 4d), as the docstring says
+    try:
+        _lpn_operator_threads(pkg)
+    finally:
+        L.gf2_set_result_side_cols(prev)
+
+
+def _lpn_operator_threads(pkg):
     import threading
     m, l = 1 << 19, 256
     a = g.random_words(m, l, 3)
