@@ -137,6 +137,32 @@ mzd_t *mzd_inv_m4ri(mzd_t *dst, mzd_t const *src, int k);
  * Returns 0, or -1 if inconsistency_check != 0 and the system has no solution. solve.rs:12-29; caller binary_matrix.rs:582-586 */
 int mzd_solve_left(mzd_t *A, mzd_t *B, int cutoff, int inconsistency_check);
 
+/* --- permutations and PLE / PLUQ (INTEGRATION.md section 3 states the contract) --- */
+/* m4ri-sys/src/mzp.rs:10-12 (opaque there): LAPACK-style transposition list, values[i] >= i */
+typedef struct mzp_t {
+  rci_t *values;
+  rci_t length;
+} mzp_t;
+mzp_t *mzp_init(rci_t length);                                      /* identity; mzp.rs:18 */
+void mzp_free(mzp_t *P);                                            /* mzp.rs:21 */
+mzp_t *mzp_init_window(mzp_t *P, rci_t begin, rci_t end);           /* values point into P's; mzp.rs:24-27 */
+void mzp_free_window(mzp_t *condemned);                             /* frees the window only */
+void Mzp_free_window(mzp_t *condemned);                             /* the spelling mzp.rs:29 declares */
+mzp_t *mzp_copy(mzp_t *P, mzp_t const *Q);                          /* P NULL: allocated; mzp.rs:32 */
+void mzp_set_ui(mzp_t *P, unsigned int value);                      /* 1: identity; anything else aborts; mzp.rs:35 */
+void mzp_print(mzp_t const *P);                                     /* one line of values; mzp.rs:38 */
+void mzd_apply_p_left(mzd_t *A, mzp_t const *P);                    /* swap rows i, P[i], i ascending; mzp.rs:41 */
+void mzd_apply_p_left_trans(mzd_t *A, mzp_t const *P);              /* the same, i descending; mzp.rs:44 */
+void mzd_apply_p_right(mzd_t *A, mzp_t const *P);                   /* swap columns i, P[i], i descending; mzp.rs:47 */
+void mzd_apply_p_right_trans(mzd_t *A, mzp_t const *P);             /* the same, i ascending; mzp.rs:50 */
+/* In place: L below the diagonal, E (mzd_ple) or U (mzd_pluq) from the diagonal on; returns the rank.  P->length must be
+ * A->nrows, Q->length A->ncols; cutoff is ignored.  The pivot rows are the row rank profile.  ple.rs:35, ple.rs:65 */
+rci_t mzd_ple(mzd_t *A, mzp_t *P, mzp_t *Q, int cutoff);
+rci_t mzd_pluq(mzd_t *A, mzp_t *P, mzp_t *Q, int cutoff);
+/* solves A0 X = B with A as mzd_pluq left it (free variables 0; B as mzd_solve_left leaves it); -1 only for an inconsistent
+ * system with check != 0.  solve.rs:53 */
+int mzd_pluq_solve_left(mzd_t const *A, rci_t rank, mzp_t const *P, mzp_t const *Q, mzd_t *B, int cutoff, int check);
+
 /* ===================================================================================== */
 /* 2. Device-resident API                                                                 */
 /* ===================================================================================== */
@@ -188,6 +214,16 @@ int gf2_equal_dev(gf2_dmat const *A, gf2_dmat const *B, int *equal, void *stream
 int gf2_echelonize_dev(gf2_dmat *A, int full, int ncols_limit, int *rank, int *pivot_cols, void *stream);
 /* Ainv = A^-1 for square A; *singular = 1 (Ainv untouched) if A has no inverse.  Synchronous. */
 int gf2_inverse_dev(gf2_dmat *Ainv, gf2_dmat const *A, int *singular, void *stream);
+/* PLE (pluq = 0) or PLUQ (pluq = 1) of a device matrix in place, the layout of mzd_ple / mzd_pluq; P (nrows ints) and Q (ncols
+ * ints) are HOST arrays that receive the transposition lists.  Synchronous. */
+int gf2_ple_dev(gf2_dmat *A, int pluq, int *P, int *Q, int *rank, void *stream);
+/* mzd_apply_p_left (right 0, trans 0), _left_trans (0, 1), _right (1, 0), _right_trans (1, 1) on a device matrix; P: host
+ * transposition list of len entries.  Synchronous. */
+int gf2_apply_p_dev(gf2_dmat *A, const int *P, int len, int right, int trans, void *stream);
+/* mzd_pluq_solve_left on the device: A as gf2_ple_dev(pluq = 1) left it, P / Q host arrays; B (max(nrows, ncols) rows or more)
+ * receives X; *inconsistent = 1 when check != 0 finds the system inconsistent.  Synchronous. */
+int gf2_pluq_solve_left_dev(gf2_dmat const *A, int rank, const int *P, const int *Q, gf2_dmat *B, int check, int *inconsistent,
+                            void *stream);
 
 /* Strassen levels a product of this shape would use right now (0 = plain M4RM): the cost model's choice, lowered until the
  * operand arena of that many levels fits into free device memory (without a device: the cost model's choice) */
@@ -265,6 +301,7 @@ int gf2_trim(void);
 int gf2_mul_host_small(mzd_t *C, mzd_t const *A, mzd_t const *B, int accumulate);      /* C (+)= A*B; 0 on success */
 int gf2_mul_nt_host_small(mzd_t *C, mzd_t const *A, mzd_t const *Bt, int accumulate);  /* C (+)= A*Bt^T */
 int gf2_echelonize_host_small(mzd_t *A, int full);                                      /* in place; returns the rank */
+int gf2_ple_host_small(mzd_t *A, int pluq, int *P, int *Q);                              /* in place; returns the rank */
 long long gf2_host_small_calls(void);
 
 /* compact binary file format for host matrices ("GF2M", version, nrows, ncols, dense little-endian rows);

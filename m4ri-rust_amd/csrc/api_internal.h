@@ -2,6 +2,7 @@
 #pragma once
 [[noreturn]] void gf2_die(const char *msg);
 #include "../../include/m4ri_hip.h"
+#include <hip/hip_runtime.h>
 mzd_t *gf2_mzd_init_uncleared(rci_t r, rci_t c);  // mzd_init without the memset (callers overwrite every word)
 // GPU-backed transpose of a host matrix (upload, 64x64-block kernel, download); 0 on success.  Used by mzd_transpose
 // for large matrices; the caller falls back to the host routine if it fails (this is not the multiply path).
@@ -19,3 +20,6 @@ void gf2_pinned_free(void *p, size_t bytes);
 // destination (allocated when DST is NULL), or nullptr when A has no side copy
 mzd_t *gf2_transpose_from_side_copy(mzd_t *DST, mzd_t const *A);
 bool gf2_mzd_block_is_pinned(mzd_t const *M);
+// error reporting of the other translation units (gf2_ple.hip): set gf2_last_error and return the error code
+int gf2_fail_msg(const char *what);
+int gf2_fail_hip(hipError_t e, const char *what);

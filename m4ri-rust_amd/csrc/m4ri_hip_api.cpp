@@ -55,6 +55,8 @@ static int fail_msg(const char *what) {
   } while (0)
 
 extern "C" const char *gf2_last_error(void) { return tls_error.c_str(); }
+int gf2_fail_msg(const char *what) { return fail_msg(what); }
+int gf2_fail_hip(hipError_t e, const char *what) { return fail(e, what); }
 
 extern "C" int gf2_device_count(void) {
   static int n = [] {

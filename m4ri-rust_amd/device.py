@@ -186,3 +186,63 @@ def prof_read(reset=True):
     n, ms = ctypes.c_int(0), ctypes.c_double(0)
     _lib.check(_lib.lib().gf2_prof_read(ctypes.byref(n), ctypes.byref(ms), int(reset)), "gf2_prof_read")
     return n.value, ms.value
+
+
+def ple(A, pluq=False, stream=None):
+    """In-place PLE (pluq=False) or PLUQ decomposition (layout of mzd_ple / mzd_pluq) -> (rank, P list, Q list)."""
+    P = (ctypes.c_int * max(A.nrows, 1))()
+    Q = (ctypes.c_int * max(A.ncols, 1))()
+    rank = ctypes.c_int(0)
+    _lib.check(_lib.lib().gf2_ple_dev(A._on(stream), int(bool(pluq)), P, Q, ctypes.byref(rank), stream), "gf2_ple_dev")
+    return rank.value, list(P[:A.nrows]), list(Q[:A.ncols])
+
+
+def apply_p(A, P, right=False, trans=False, stream=None):
+    """mzd_apply_p_left / _left_trans / _right / _right_trans on a device matrix; P: transposition list."""
+    arr = (ctypes.c_int * max(len(P), 1))(*P)
+    _lib.check(_lib.lib().gf2_apply_p_dev(A._on(stream), arr, len(P), int(bool(right)), int(bool(trans)), stream),
+               "gf2_apply_p_dev")
+    return A
+
+
+def pluq_solve_left(A, rank, P, Q, B, check=True, stream=None):
+    """Solve A0 X = B in place in B with A as ple(pluq=True) left it -> False if check finds the system inconsistent."""
+    pa = (ctypes.c_int * max(len(P), 1))(*P)
+    qa = (ctypes.c_int * max(len(Q), 1))(*Q)
+    bad = ctypes.c_int(0)
+    _lib.check(_lib.lib().gf2_pluq_solve_left_dev(A._on(stream), rank, pa, qa, B._on(stream), int(bool(check)),
+                                                  ctypes.byref(bad), stream), "gf2_pluq_solve_left_dev")
+    return not bad.value
+
+
+class Mzp:
+    """Owner of an mzp_t (mzp_init / mzp_free) for tests and ctypes callers."""
+
+    def __init__(self, length=None, _ptr=None, _window=False):
+        self.ptr = _ptr if _ptr is not None else _lib.lib().mzp_init(length)
+        self._window = _window
+
+    @staticmethod
+    def from_list(values):
+        p = Mzp(len(values))
+        for i, v in enumerate(values):
+            p.ptr.contents.values[i] = v
+        return p
+
+    def window(self, begin, end):
+        return Mzp(_ptr=_lib.lib().mzp_init_window(self.ptr, begin, end), _window=True)
+
+    def __len__(self):
+        return self.ptr.contents.length
+
+    def to_list(self):
+        z = self.ptr.contents
+        return [z.values[i] for i in range(z.length)]
+
+    def __del__(self):
+        if getattr(self, "ptr", None):
+            try:
+                (_lib.lib().mzp_free_window if self._window else _lib.lib().mzp_free)(self.ptr)
+            except Exception:
+                pass
+            self.ptr = None
