@@ -460,3 +460,110 @@ int oracle_solve_left(const u64 *A, int lda, int m, int n, u64 *B, int ldb, int 
   free(piv);
   return bad ? -1 : 0;
 }
+
+/* ---- PLE / PLUQ and transposition lists ----------------------
+ * Written from the contract alone: column-greedy elimination in which the pivot of column c is the first remaining row, in
+ * input order, whose reduced word has bit c.  Every remaining row with bit c is reduced by it (and records the pivot's index
+ * in its L word); the rows that never become pivots keep their input order.  About m * n * r / 64 word operations. */
+static inline void swap_bits(u64 *row, int a, int b) {
+  const u64 x = ((row[a >> 6] >> (a & 63)) ^ (row[b >> 6] >> (b & 63))) & 1;
+  row[a >> 6] ^= x << (a & 63);
+  row[b >> 6] ^= x << (b & 63);
+}
+
+int oracle_ple(u64 *M, int ld, int m, int n, int pluq, int *P, int *Q) {
+  const int w = width_of(n), kmax = m < n ? m : n, lw = width_of(kmax > 0 ? kmax : 1);
+  for (int j = 0; j < n; ++j) Q[j] = j;
+  for (int i = 0; i < m; ++i) P[i] = i;
+  if (m <= 0 || n <= 0) return 0;
+  u64 *cur = (u64 *)malloc((size_t)m * w * sizeof(u64));
+  u64 *L = (u64 *)calloc((size_t)m * lw, sizeof(u64));
+  int *rest = (int *)malloc((size_t)m * sizeof(int)), *sigma = (int *)malloc((size_t)m * sizeof(int));
+  for (int i = 0; i < m; ++i) {
+    memcpy(cur + (size_t)i * w, M + (size_t)i * ld, (size_t)w * sizeof(u64));
+    cur[(size_t)i * w + w - 1] &= tail_mask(n);
+    rest[i] = i;
+  }
+  int nrest = m, r = 0;
+  for (int c = 0; c < n && nrest > 0; ++c) {
+    const int cw = c >> 6;
+    const u64 bit = 1ull << (c & 63);
+    int at = 0;
+    while (at < nrest && !(cur[(size_t)rest[at] * w + cw] & bit)) ++at;
+    if (at == nrest) continue;
+    const int p = rest[at];
+    const u64 *e = cur + (size_t)p * w;
+    for (int t = at + 1; t < nrest; ++t) {
+      u64 *row = cur + (size_t)rest[t] * w;
+      if (row[cw] & bit) {
+        for (int j = cw; j < w; ++j) row[j] ^= e[j]; /* e is zero left of column c */
+        L[(size_t)rest[t] * lw + (r >> 6)] |= 1ull << (r & 63);
+      }
+    }
+    memmove(rest + at, rest + at + 1, (size_t)(nrest - at - 1) * sizeof(int));
+    --nrest;
+    sigma[r] = p;
+    Q[r] = c;
+    ++r;
+  }
+  memcpy(sigma + r, rest, (size_t)nrest * sizeof(int));
+  /* in place: row i < r = L[i][0, i) | E_i (U_i for PLUQ); row i >= r = L[i][0, r) */
+  for (int i = 0; i < m; ++i) {
+    u64 *row = M + (size_t)i * ld;
+    const u64 *lrow = L + (size_t)sigma[i] * lw;
+    const int lim = i < r ? i : r;
+    if (i < r) {
+      memcpy(row, cur + (size_t)sigma[i] * w, (size_t)w * sizeof(u64));
+      if (pluq)
+        for (int t = 0; t < r; ++t)
+          if (Q[t] != t) swap_bits(row, t, Q[t]);
+    } else {
+      memset(row, 0, (size_t)w * sizeof(u64));
+    }
+    for (int j = 0; j < width_of(lim); ++j) {
+      const int bits = lim - 64 * j;
+      row[j] |= lrow[j] & (bits >= 64 ? ~0ull : ((1ull << bits) - 1));
+    }
+  }
+  /* sigma (position i holds input row sigma[i]) -> transpositions: swapping i and P[i] ascending reproduces it */
+  int *pos = rest, *at = (int *)malloc((size_t)m * sizeof(int));
+  for (int i = 0; i < m; ++i) pos[i] = at[i] = i;
+  for (int i = 0; i < m; ++i) {
+    const int p = pos[sigma[i]], a = at[i], b = at[p];
+    P[i] = p;
+    at[i] = b;
+    at[p] = a;
+    pos[a] = p;
+    pos[b] = i;
+  }
+  free(at);
+  free(cur);
+  free(L);
+  free(rest);
+  free(sigma);
+  return r;
+}
+
+void oracle_apply_p(u64 *M, int ld, int m, int n, const int *P, int len, int right, int trans) {
+  const int w = width_of(n);
+  if (!right) {
+    const int k = len < m ? len : m;
+    for (int s = 0; s < k; ++s) {
+      const int i = trans ? k - 1 - s : s, j = P[i];
+      if (j == i) continue;
+      u64 *a = M + (size_t)i * ld, *b = M + (size_t)j * ld;
+      for (int q = 0; q < w; ++q) {
+        const u64 t = a[q];
+        a[q] = b[q];
+        b[q] = t;
+      }
+    }
+    return;
+  }
+  const int k = len < n ? len : n;
+  for (int s = 0; s < k; ++s) {
+    const int i = trans ? s : k - 1 - s, j = P[i];
+    if (j != i)
+      for (int row = 0; row < m; ++row) swap_bits(M + (size_t)row * ld, i, j);
+  }
+}

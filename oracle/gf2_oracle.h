@@ -96,6 +96,16 @@ int oracle_inverse(uint64_t *Ainv, int ldi, const uint64_t *A, int lda, int n);
  * first m rows): B's first n rows become X with free variables 0, the rest 0.  Returns 0, or -1 if inconsistent. */
 int oracle_solve_left(const uint64_t *A, int lda, int m, int n, uint64_t *B, int ldb, int brows, int k);
 
+/* ---- PLE / PLUQ ---------------------------------------------------
+ * mzd_ple (pluq == 0) / mzd_pluq (pluq != 0) of the m x n matrix M, in place with the contract's layout: the pivot rows are the
+ * row rank profile ordered by pivot column, then the other rows in input order; row i < r holds L[i][0, i) and E_i (U_i), row
+ * i >= r holds L[i][0, r).  P (m entries) and Q (n entries) receive the transposition lists.  Returns the rank r.
+ * Plain column-greedy elimination, written from the contract; it shares no code with the library. */
+int oracle_ple(uint64_t *M, int ld, int m, int n, int pluq, int *P, int *Q);
+/* mzd_apply_p_left (right == 0, trans == 0): rows (i, P[i]) swapped for i ascending over min(len, m); _left_trans descending;
+ * mzd_apply_p_right (right != 0): columns (i, P[i]) swapped for i descending over min(len, n); _right_trans ascending. */
+void oracle_apply_p(uint64_t *M, int ld, int m, int n, const int *P, int len, int right, int trans);
+
 #ifdef __cplusplus
 }
 #endif

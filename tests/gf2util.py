@@ -53,6 +53,11 @@ def oracle():
         lib.oracle_inverse.restype = _I
         lib.oracle_solve_left.argtypes = [_U64P, _I, _I, _I, _U64P, _I, _I, _I]
         lib.oracle_solve_left.restype = _I
+        _IP = ctypes.POINTER(_I)
+        lib.oracle_ple.argtypes = [_U64P, _I, _I, _I, _I, _IP, _IP]
+        lib.oracle_ple.restype = _I
+        lib.oracle_apply_p.argtypes = [_U64P, _I, _I, _I, _IP, _I, _I, _I]
+        lib.oracle_apply_p.restype = None
         for f in ("oracle_fill_random", "oracle_mul_bits", "oracle_mul_naive", "oracle_mul_fast",
                   "oracle_mul_naive_t", "oracle_mul_m4rm", "oracle_mul_strassen", "oracle_mul_va",
                   "oracle_transpose", "oracle_add"):
@@ -174,3 +179,25 @@ def o_solve_left(a, m, n, b, brows, k):
     x = np.ascontiguousarray(b).copy()
     rc = oracle().oracle_solve_left(ptr(a), a.shape[1], m, n, ptr(x), x.shape[1], brows, k)
     return x, rc == 0
+
+
+def _iptr(a):
+    assert a.dtype == np.int32 and a.flags["C_CONTIGUOUS"]
+    return a.ctypes.data_as(ctypes.POINTER(_I))
+
+
+def o_ple(a, nrows, ncols, pluq=False):
+    """-> (rank, P, Q, in-place result) of mzd_ple / mzd_pluq on a copy of `a` (oracle_ple); P, Q: int32 arrays."""
+    m = np.ascontiguousarray(a).copy()
+    P = np.zeros(max(nrows, 1), dtype=np.int32)
+    Q = np.zeros(max(ncols, 1), dtype=np.int32)
+    rank = oracle().oracle_ple(ptr(m), m.shape[1], nrows, ncols, 1 if pluq else 0, _iptr(P), _iptr(Q))
+    return rank, P[:nrows], Q[:ncols], m
+
+
+def o_apply_p(a, nrows, ncols, P, right=False, trans=False):
+    """mzd_apply_p_left / _left_trans / _right / _right_trans on a copy of `a` (oracle_apply_p)."""
+    m = np.ascontiguousarray(a).copy()
+    p = np.ascontiguousarray(np.asarray(P, dtype=np.int32))
+    oracle().oracle_apply_p(ptr(m), m.shape[1], nrows, ncols, _iptr(p), len(p), int(bool(right)), int(bool(trans)))
+    return m

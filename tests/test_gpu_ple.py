@@ -12,6 +12,7 @@ import pytest
 
 import gf2util as g
 import ple_ref as R
+from ple_cases import low_rank, structured
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -32,30 +33,6 @@ def mode(request, monkeypatch):
     else:
         monkeypatch.setenv("M4RI_HIP_HOST_SMALL_WORK", "0")
     return request.param
-
-
-def low_rank(m, n, r, seed):
-    if r == 0:
-        return np.zeros((m, g.width(n)), dtype=np.uint64)
-    return g.o_mul_naive(g.random_words(m, r, seed), g.random_words(r, n, seed + 1), m, r, n)
-
-
-def structured(m, n):
-    yield np.zeros((m, g.width(n)), dtype=np.uint64)
-    k = min(m, n)
-    eye = np.zeros((m, n), dtype=np.uint8)
-    eye[np.arange(k), np.arange(k)] = 1
-    yield g.bits_to_words(eye)
-    yield g.bits_to_words(eye[::-1].copy())
-    base = g.random_words(max(m // 3, 1), n, 11)
-    yield np.ascontiguousarray(np.vstack([base] * 4)[:m])
-    lz = g.words_to_bits(low_rank(m, n, min(m, n) // 3, 12), n)
-    lz[:, :min(n, 70)] = 0
-    yield g.bits_to_words(lz)
-    yield np.ascontiguousarray(np.repeat(g.random_words(1, n, 13), m, axis=0))
-    one = np.zeros((m, n), dtype=np.uint8)
-    one[:, n // 2] = np.arange(m) % 3 == 1
-    yield g.bits_to_words(one)
 
 
 def host_ple(pkg, a, m, n, pluq):
@@ -206,13 +183,22 @@ def check_large(pkg, a, m, n, certificate):
             bits = g.words_to_bits(Ew, n) if rank else np.zeros((0, n), np.uint8)
             assert all(int(np.argmax(bits[k])) == Q[k] for k in range(rank))
             if certificate:
+                # with P A0 = L E above and E of full row rank, this makes the pivot rows the row rank profile
                 sigma = R.apply_left(list(range(m)), P)
                 lb = g.words_to_bits(Lw, max(rank, 1))[:, :rank]
                 piv_rows = np.array(sigma[:rank])
                 for i in range(rank, m):
                     ks = np.nonzero(lb[i])[0]
                     assert (piv_rows[ks] < sigma[i]).all(), "a non-pivot row depends on a later pivot row"
-                assert sorted(sigma[:rank]) == sorted(piv_rows.tolist())
+        check_orders(P, Q, rank, m)
+
+
+def check_orders(P, Q, rank, m):
+    """P is a permutation whose non-pivot rows keep their input order; Q[:rank] (the pivot columns) strictly increases."""
+    sigma = np.array(R.apply_left(list(range(m)), P))
+    assert np.array_equal(np.sort(sigma), np.arange(m)), "P does not realise a permutation"
+    assert (np.diff(sigma[rank:]) > 0).all(), "the non-pivot rows are not in their original order"
+    assert (np.diff(np.asarray(Q[:rank])) > 0).all(), "the pivot columns do not increase"
 
 
 @pytest.mark.parametrize("kind", ["random", "rank10000"])
@@ -252,6 +238,7 @@ def check_on_device(pkg, src, n, want_rank):
         t, A = copy_of_src()
         rank, P, Q = device.ple(A, pluq=pluq)
         assert rank == er and Q[:rank] == piv and Q[rank:] == list(range(rank, n))
+        check_orders(P, Q, rank, n)
         t2, A2 = copy_of_src()
         assert device.ple(A2, pluq=pluq) == (rank, P, Q) and device.equal(A, A2), "two runs differ"
         del t2, A2
