@@ -2566,6 +2566,17 @@ __global__ __launch_bounds__(256) void gf2_strassen_split_kernel(u64 *__restrict
     }
   }
 }
+__device__ __forceinline__ uint4 nt_load4(const uint4 *p) {
+  const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void nt_store4(uint4 v, uint4 *p) {
+  const u32x4 x = {v.x, v.y, v.z, v.w};
+  __builtin_nontemporal_store(x, reinterpret_cast<u32x4 *>(p));
+}
+
+// non-temporal loads and stores: each product word is read once and each word of C written once (measured at 65536^3: 0.30 ->
+// 0.24-0.27 ms; non-temporal loads alone gain nothing)
 __global__ __launch_bounds__(256) void gf2_strassen_merge_kernel(u64 *__restrict__ dst, long long ldd, long long dstStride,
                                                                  const u64 *__restrict__ src, long long lds_,
                                                                  long long srcStride, int h, int w, int accumulate) {
@@ -2579,7 +2590,7 @@ __global__ __launch_bounds__(256) void gf2_strassen_merge_kernel(u64 *__restrict
     const int r = (int)(idx / pairs), c = (int)(idx % pairs) * 2;
     uint4 m[7];
 #pragma unroll
-    for (int q = 0; q < 7; ++q) m[q] = *reinterpret_cast<const uint4 *>(M + q * srcStride + (long long)r * lds_ + c);
+    for (int q = 0; q < 7; ++q) m[q] = nt_load4(reinterpret_cast<const uint4 *>(M + q * srcStride + (long long)r * lds_ + c));
     uint4 c11 = xor4(xor4(m[0], m[3]), xor4(m[4], m[6]));
     uint4 c12 = xor4(m[2], m[4]);
     uint4 c21 = xor4(m[1], m[3]);
@@ -2594,10 +2605,10 @@ __global__ __launch_bounds__(256) void gf2_strassen_merge_kernel(u64 *__restrict
       c21 = xor4(c21, *p21);
       c22 = xor4(c22, *p22);
     }
-    *p11 = c11;
-    *p12 = c12;
-    *p21 = c21;
-    *p22 = c22;
+    nt_store4(c11, p11);
+    nt_store4(c12, p12);
+    nt_store4(c21, p21);
+    nt_store4(c22, p22);
   }
 }
 
@@ -2744,7 +2755,7 @@ __global__ __launch_bounds__(256) void gf2_strassen_merge2_kernel(u64 *__restric
 // values, q3 -> one word to store.  Each source word is read once and each destination word written once: 64 + 343 block
 // units, against (16 + 49) + 49 (16 + 49) / 16 = 264 for two fused-pair passes in the same unit -- the intermediate
 // level is never written or re-read.
-// Virtual level: blockIdx.y = q0 picks ONE or TWO quadrants of the grandparent matrix (src0[q0], src1[q0] or null) whose
+// Virtual level: group q0 (blockIdx.x % groups) picks ONE or TWO quadrants of the grandparent matrix (src0[q0], src1[q0] or null) whose
 // XOR is the source operand, so that four levels cost one read of (12 / 4 of) the matrix and one write of the 2401 leaves.
 // Accesses are 8 bytes per lane (512 contiguous bytes per wave and stream): the register budget is what sets the width.
 // PACK: row-group-packed output for the paired tile kernels (see gf2_strassen_split2_kernel).
@@ -2763,18 +2774,22 @@ __device__ constexpr int kStrassenSupp[2][7][2] = {
 template <int SIDE, bool PACK, bool NT = false>
 __global__ __launch_bounds__(256) void gf2_strassen_split3_kernel(u64 *__restrict__ dst, long long ldd, long long dstStride,
                                                                   const gf2k_split3_srcs srcs, long long lds_,
-                                                                  long long srcStride, int h, int w) {
+                                                                  long long srcStride, int h, int w, int nx) {
   // h, w: rows / words of one OUTPUT operand (an eighth of the source operand in each dimension)
-  const int b = blockIdx.z, g = blockIdx.y;
+  // blockIdx.x = nx position blocks x groups, the group fastest: the up to seven workgroups that read one position block of the
+  // four grandparent quadrants (each quadrant feeds two to four groups) run side by side, so that its re-reads hit the caches
+  // instead of HBM (with the group slowest, 1.4 GB of stores lay between two reads of a quadrant word: 12 quadrants from HBM)
+  const int b = blockIdx.z, groups = gridDim.x / nx;
+  const int g = blockIdx.x % groups, xb = blockIdx.x / groups;
   const u64 *X0 = srcs.a[g] + (long long)b * srcStride;
   const u64 *X1 = srcs.b[g] ? srcs.b[g] + (long long)b * srcStride : nullptr;
-  u64 *Y = dst + ((long long)b * gridDim.y + g) * 343 * dstStride;
+  u64 *Y = dst + ((long long)b * groups + g) * 343 * dstStride;
   const long long total = (long long)h * w;
   // PACK with w % 16 == 0: a workgroup takes a tile of 16 rows x 16 words -- wave v the words 4v..4v+3, lane L row L % 16 of
   // word L / 16 -- so that its reads are whole 128-byte lines (a lane-per-row mapping touches 64 lines per load and ran at
   // half the bandwidth) and its packed stores 128-byte runs (16 rows of one 64-bit column); tiles in packed-address order
   const bool tiled = PACK && (w & 15) == 0;
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+  for (long long idx = (long long)xb * blockDim.x + threadIdx.x; idx < total; idx += (long long)nx * blockDim.x) {
     int r, c;
     if (tiled) {
       const long long tile = idx >> 8;           // 256 positions per tile
@@ -2845,7 +2860,8 @@ __device__ constexpr int kStrassenFoldTo[7][2] = {{0, 3}, {2, 3}, {1, 3}, {0, 2}
 // thread owns one 64-bit word position: it loads the 343 product words as it goes (seven at a time) and keeps the 64
 // results in registers.  blockIdx.y = g: several independent parents per batch element (the seven level-1 products of a
 // four-level plan), parent (b * gridDim.y + g) at dst + that * dstStride.
-template <bool NTL>
+// NT: non-temporal loads (the products are read once) and stores (the results are not re-read by this pass)
+template <bool NT>
 __global__ __launch_bounds__(256) void gf2_strassen_merge3_kernel(u64 *__restrict__ dst, long long ldd, long long dstStride,
                                                                   const u64 *__restrict__ src, long long lds_,
                                                                   long long srcStride, int h, int w, int accumulate) {
@@ -2871,7 +2887,7 @@ __global__ __launch_bounds__(256) void gf2_strassen_merge3_kernel(u64 *__restric
         u64 m[7];
         static_for<7>([&](auto Q3) {
           constexpr int q3 = decltype(Q3)::value;
-          m[q3] = NTL ? __builtin_nontemporal_load(&Mq[(long long)(7 * q2 + q3) * srcStride]) : Mq[(long long)(7 * q2 + q3) * srcStride];
+          m[q3] = NT ? __builtin_nontemporal_load(&Mq[(long long)(7 * q2 + q3) * srcStride]) : Mq[(long long)(7 * q2 + q3) * srcStride];
         });
         const u64 f[4] = {m[0] ^ m[3] ^ m[4] ^ m[6], m[2] ^ m[4], m[1] ^ m[3], m[0] ^ m[1] ^ m[2] ^ m[5]};
         constexpr int t0 = kStrassenFoldTo[q2][0], t1 = kStrassenFoldTo[q2][1];
@@ -2898,7 +2914,8 @@ __global__ __launch_bounds__(256) void gf2_strassen_merge3_kernel(u64 *__restric
       u64 *pd = Cq + (long long)(r + R * h) * ldd + (long long)Cc * w + c;
       u64 v = z[k];
       if (accumulate) v ^= *pd;
-      *pd = v;
+      if (NT) __builtin_nontemporal_store(v, pd);
+      else *pd = v;
     });
   }
 }
@@ -3853,22 +3870,22 @@ extern "C" hipError_t gf2k_strassen_split3(u64 *dst, long long ldd, long long ds
   const long long total = (long long)h * w;
   static const int cap = GF2K_DEV_ENV("M4RI_HIP_PASS_GRID", 8192);
   const int gx = grid_for(total, 256, (cap + batch * groups - 1) / (batch * groups));
-  const dim3 grid(gx, groups, batch);
+  const dim3 grid(gx * groups, 1, batch);  // gx position blocks x groups, the group fastest (see the kernel)
   // non-temporal stores: the 343 operand streams are not re-read before the leaf launch (measured: -3 % / -6 % pass time)
   static const int nt = GF2K_DEV_ENV("M4RI_HIP_PASS_NT", 1);
 #ifdef GF2K_DEV_VARIANTS  // (the plain-store forms exist for A/B runs only: no instantiation the shipped launcher cannot reach)
   if (!nt && side == 2)
-    hipLaunchKernelGGL((gf2_strassen_split3_kernel<0, true>), grid, dim3(256), 0, stream, dst, ldd, dstStride, srcs, lds_, srcStride, h, w);
+    hipLaunchKernelGGL((gf2_strassen_split3_kernel<0, true>), grid, dim3(256), 0, stream, dst, ldd, dstStride, srcs, lds_, srcStride, h, w, gx);
   else if (!nt && side == 1)
-    hipLaunchKernelGGL((gf2_strassen_split3_kernel<1, false>), grid, dim3(256), 0, stream, dst, ldd, dstStride, srcs, lds_, srcStride, h, w);
+    hipLaunchKernelGGL((gf2_strassen_split3_kernel<1, false>), grid, dim3(256), 0, stream, dst, ldd, dstStride, srcs, lds_, srcStride, h, w, gx);
   else
 #endif
   if (side == 2)
-    hipLaunchKernelGGL((gf2_strassen_split3_kernel<0, true, true>), grid, dim3(256), 0, stream, dst, ldd, dstStride, srcs, lds_, srcStride, h, w);
+    hipLaunchKernelGGL((gf2_strassen_split3_kernel<0, true, true>), grid, dim3(256), 0, stream, dst, ldd, dstStride, srcs, lds_, srcStride, h, w, gx);
   else if (side == 0)
-    hipLaunchKernelGGL((gf2_strassen_split3_kernel<0, false>), grid, dim3(256), 0, stream, dst, ldd, dstStride, srcs, lds_, srcStride, h, w);
+    hipLaunchKernelGGL((gf2_strassen_split3_kernel<0, false>), grid, dim3(256), 0, stream, dst, ldd, dstStride, srcs, lds_, srcStride, h, w, gx);
   else
-    hipLaunchKernelGGL((gf2_strassen_split3_kernel<1, false, true>), grid, dim3(256), 0, stream, dst, ldd, dstStride, srcs, lds_, srcStride, h, w);
+    hipLaunchKernelGGL((gf2_strassen_split3_kernel<1, false, true>), grid, dim3(256), 0, stream, dst, ldd, dstStride, srcs, lds_, srcStride, h, w, gx);
   (void)nt;
   return hipGetLastError();
 }
@@ -3881,7 +3898,8 @@ extern "C" hipError_t gf2k_strassen_merge3(u64 *dst, long long ldd, long long ds
   if (h <= 0 || w <= 0 || batch <= 0 || groups <= 0) return hipSuccess;
   const long long total = (long long)h * w;
   const int gx = grid_for(total, 256, (8192 + batch * groups - 1) / (batch * groups));
-  static const int ntl = GF2K_DEV_ENV("M4RI_HIP_PASS_NTL", 1);  // the products are read once: non-temporal loads, -7 % (1.25 -> 1.15 ms)
+  // non-temporal loads: -7 % (1.25 -> 1.15 ms); and stores: 1.11-1.16 -> 1.06-1.09 ms at 65536^3
+  static const int ntl = GF2K_DEV_ENV("M4RI_HIP_PASS_NTL", 1);
 #ifdef GF2K_DEV_VARIANTS
   if (!ntl)
     hipLaunchKernelGGL(gf2_strassen_merge3_kernel<false>, dim3(gx, groups, batch), dim3(256), 0, stream, dst, ldd, dstStride, src, lds_,
