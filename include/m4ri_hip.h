@@ -163,6 +163,18 @@ rci_t mzd_pluq(mzd_t *A, mzp_t *P, mzp_t *Q, int cutoff);
  * system with check != 0.  solve.rs:53 */
 int mzd_pluq_solve_left(mzd_t const *A, rci_t rank, mzp_t const *P, mzp_t const *Q, mzd_t *B, int cutoff, int check);
 
+/* --- triangular solves (M4RI triangular.h; not declared by m4ri-sys: INTEGRATION.md gives the extern block) ---
+ * T is square and unit triangular: only its strict lower (upper) triangle is read, the diagonal counts as 1, and the other
+ * triangle and the diagonal may hold anything -- a window of the first r rows and columns of what mzd_pluq leaves serves as L
+ * and as U.  X replaces B; it is unique, so every bit is defined, and the device path and the host routine of the size
+ * dispatch agree bit for bit.  T and B may be windows, also of one parent, as long as their regions do not overlap; bits of a
+ * parent outside B's window do not change.  cutoff (recursion cutoff of the CPU algorithm) is accepted and ignored.  A
+ * non-square T or a dimension mismatch aborts, as m4ri_die does; so does a device failure.  n = 0 or an empty B: nothing to do. */
+void mzd_trsm_lower_left (mzd_t const *L, mzd_t *B, int cutoff);  /* L X = B,  L n x n, B n x k; X in place of B */
+void mzd_trsm_upper_left (mzd_t const *U, mzd_t *B, int cutoff);  /* U X = B */
+void mzd_trsm_lower_right(mzd_t const *L, mzd_t *B, int cutoff);  /* X L = B,  B k x n */
+void mzd_trsm_upper_right(mzd_t const *U, mzd_t *B, int cutoff);  /* X U = B */
+
 /* ===================================================================================== */
 /* 2. Device-resident API                                                                 */
 /* ===================================================================================== */
@@ -224,6 +236,11 @@ int gf2_apply_p_dev(gf2_dmat *A, const int *P, int len, int right, int trans, vo
  * receives X; *inconsistent = 1 when check != 0 finds the system inconsistent.  Synchronous. */
 int gf2_pluq_solve_left_dev(gf2_dmat const *A, int rank, const int *P, const int *Q, gf2_dmat *B, int check, int *inconsistent,
                             void *stream);
+/* device-resident: B = T^-1 B (right == 0) or B T^-1 (right != 0); upper selects the triangle.  The contract of mzd_trsm_* above:
+ * only the strict triangle of T is read, B's bits alone change (the excess bits of its last word stay zero; a view's neighbours stay
+ * as they are).  A non-square T or a dimension mismatch returns -1 and sets gf2_last_error; n = 0 or an empty B returns 0 without a
+ * launch.  Asynchronous on `stream`, like gf2_mul_dev: one launch inverts the diagonal blocks, the rest is products. */
+int gf2_trsm_dev(gf2_dmat const *T, gf2_dmat *B, int upper, int right, void *stream);
 
 /* Strassen levels a product of this shape would use right now (0 = plain M4RM): the cost model's choice, lowered until the
  * operand arena of that many levels fits into free device memory (without a device: the cost model's choice) */
@@ -302,6 +319,9 @@ int gf2_mul_host_small(mzd_t *C, mzd_t const *A, mzd_t const *B, int accumulate)
 int gf2_mul_nt_host_small(mzd_t *C, mzd_t const *A, mzd_t const *Bt, int accumulate);  /* C (+)= A*Bt^T */
 int gf2_echelonize_host_small(mzd_t *A, int full);                                      /* in place; returns the rank */
 int gf2_ple_host_small(mzd_t *A, int pluq, int *P, int *Q);                              /* in place; returns the rank */
+/* host routine of the size dispatch of mzd_trsm_* (work = n * n * ceil(k / 64)), exported for tests without a device; 0 on
+ * success, -1 for a non-square T or a dimension mismatch */
+int gf2_trsm_host_small(mzd_t const *T, mzd_t *B, int upper, int right);
 long long gf2_host_small_calls(void);
 
 /* compact binary file format for host matrices ("GF2M", version, nrows, ncols, dense little-endian rows);

@@ -101,6 +101,10 @@ _PROTOS = {
     "mzd_ple": (_I, [MzdP, MzpP, MzpP, _I]),
     "mzd_pluq": (_I, [MzdP, MzpP, MzpP, _I]),
     "mzd_pluq_solve_left": (_I, [MzdP, _I, MzpP, MzpP, MzdP, _I, _I]),
+    "mzd_trsm_lower_left": (None, [MzdP, MzdP, _I]),
+    "mzd_trsm_upper_left": (None, [MzdP, MzdP, _I]),
+    "mzd_trsm_lower_right": (None, [MzdP, MzdP, _I]),
+    "mzd_trsm_upper_right": (None, [MzdP, MzdP, _I]),
     "mzd_mul_m4rm": (MzdP, [MzdP, MzdP, MzdP, _I]),
     "mzd_addmul_m4rm": (MzdP, [MzdP, MzdP, MzdP, _I]),
     "mzd_mul": (MzdP, [MzdP, MzdP, MzdP, _I]),
@@ -136,6 +140,7 @@ _PROTOS = {
     "gf2_apply_p_dev": (_I, [DMatP, ctypes.POINTER(_I), _I, _I, _I, ctypes.c_void_p]),
     "gf2_pluq_solve_left_dev": (_I, [DMatP, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), DMatP, _I, ctypes.POINTER(_I),
                                      ctypes.c_void_p]),
+    "gf2_trsm_dev": (_I, [DMatP, DMatP, _I, _I, ctypes.c_void_p]),
     "gf2_mul_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I, _I, _I]),
     "gf2_mul_multi": (MzdP, [MzdP, MzdP, MzdP, _I, _I, ctypes.POINTER(_I), _I]),
     "gf2_mzd_cache_on_device": (_I, [MzdP]),
@@ -147,6 +152,7 @@ _PROTOS = {
     "gf2_mul_nt_host_small": (_I, [MzdP, MzdP, MzdP, _I]),
     "gf2_echelonize_host_small": (_I, [MzdP, _I]),
     "gf2_ple_host_small": (_I, [MzdP, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "gf2_trsm_host_small": (_I, [MzdP, MzdP, _I, _I]),
     "gf2_host_small_calls": (ctypes.c_longlong, []),
     "gf2_mzd_save": (_I, [ctypes.c_char_p, MzdP]),
     "gf2_mzd_load": (MzdP, [ctypes.c_char_p]),

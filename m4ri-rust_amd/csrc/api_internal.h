@@ -23,3 +23,8 @@ bool gf2_mzd_block_is_pinned(mzd_t const *M);
 // error reporting of the other translation units (gf2_ple.hip): set gf2_last_error and return the error code
 int gf2_fail_msg(const char *what);
 int gf2_fail_hip(hipError_t e, const char *what);
+// scratch from the per-stream arena of m4ri_hip_api.cpp (grown on demand, reused by later calls on the stream, released by
+// gf2_trim); slots 0-3 belong to the products, 4 / 5 to gf2_trsm.hip (block inverses / a leaf's result)
+int gf2_stream_scratch(hipStream_t s, size_t bytes, void **out, int slot);
+// counts a run of a host routine of the size dispatch (gf2_host_small_calls)
+void gf2_note_host_small_call();

@@ -6,7 +6,7 @@
 //   the chunks in row order and runs the column-greedy elimination on the <= 64 pivot rows, ple_panel_apply writes every row's
 //   L word (its coordinates in the basis E) and the panel's row order.
 //   otherwise, split at a multiple of 64: left half; gather the right half's rows by the left order; E12 = L11^-1 A12
-//   (ple_trsm64 leaves, gf2_mul_dev above them); A22 ^= L21 E12 (gf2_mul_dev, the n^3 part); right half; gather L21's rows
+//   (gf2_trsm_dev, gf2_trsm.hip: block inverses and products); A22 ^= L21 E12 (gf2_mul_dev, the n^3 part); right half; gather L21's rows
 //   by the right order; move the right L next to the left one (ple_compress_*).
 // Non-pivot rows keep their relative order at every level, so the pivot rows are the row rank profile (the contract in
 // INTEGRATION.md section 3).  Every kernel masks the excess bits of a row's last word: windows of dirty parents stay intact.
@@ -238,49 +238,6 @@ __global__ void __launch_bounds__(256) ple_tri(u64 *dst, long long ldd, const u6
   else *d = (*d & (low | ~valid)) | (v & ~low & valid);
 }
 
-// Triangular solve with a unit-diagonal 64 x 64 block T (nr <= 64 rows, T's word column at T, row stride ldt): lower: row i of
-// X = B_i ^ sum_{k < i} T[i][k] X_k; upper: X_i = B_i ^ sum_{i < k < nr} T[i][k] X_k.  One thread per word of B; the rows of
-// B live in registers.  Only B's bits under the word masks change.
-template <bool UPPER>
-__global__ void __launch_bounds__(64) ple_trsm64(const u64 *T, long long ldt, int nr, u64 *B, long long ldb, int words, u64 lastmask) {
-  const int w = blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= words) return;
-  const u64 m = w == words - 1 ? lastmask : ~0ull;
-  u64 x[64];
-#pragma unroll
-  for (int i = 0; i < 64; ++i) x[i] = i < nr ? B[(long long)i * ldb + w] : 0;
-  const u64 nrmask = nr >= 64 ? ~0ull : ((1ull << nr) - 1);
-  if (!UPPER) {
-#pragma unroll
-    for (int i = 1; i < 64; ++i) {
-      if (i < nr) {
-        const u64 l = T[(long long)i * ldt] & ((1ull << i) - 1);
-        u64 acc = x[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) acc ^= ((l >> k) & 1) ? x[k] : 0ull;
-        x[i] = acc;
-      }
-    }
-  } else {
-#pragma unroll
-    for (int i = 62; i >= 0; --i) {
-      if (i < nr - 1) {
-        const u64 u = T[(long long)i * ldt] & nrmask & ~((2ull << i) - 1);
-        u64 acc = x[i];
-#pragma unroll
-        for (int k = i + 1; k < 64; ++k) acc ^= ((u >> k) & 1) ? x[k] : 0ull;
-        x[i] = acc;
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 64; ++i)
-    if (i < nr) {
-      u64 *d = B + (long long)i * ldb + w;
-      *d = (*d & ~m) | (x[i] & m);
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------------
@@ -333,35 +290,6 @@ int gather_rows(const gf2_dmat &D, const int *perm_dev, int rows, int words, u64
   return 0;
 }
 
-// X = T^-1 X for the unit lower (upper) triangular nr x nr matrix T whose row 0 / column 0 is at (tr, tc) of A (tc multiple of
-// 64); X: nr rows of B from row xr, columns [xc, xc + xcols) (xc multiple of 64)
-int trsm(const gf2_dmat &A, long long tr, long long tc, int nr, const gf2_dmat &B, long long xr, long long xc, int xcols, bool upper,
-         hipStream_t s) {
-  if (nr <= 0 || xcols <= 0) return 0;
-  const int words = words_of(xcols);
-  if (nr <= 64) {
-    const u64 *T = static_cast<const u64 *>(A.data) + tr * A.ld + (tc >> 6);
-    u64 *X = static_cast<u64 *>(B.data) + xr * B.ld + (xc >> 6);
-    if (upper)
-      hipLaunchKernelGGL(ple_trsm64<true>, dim3(grid_of(words, 64)), dim3(64), 0, s, T, A.ld, nr, X, B.ld, words, last_mask(xcols));
-    else
-      hipLaunchKernelGGL(ple_trsm64<false>, dim3(grid_of(words, 64)), dim3(64), 0, s, T, A.ld, nr, X, B.ld, words, last_mask(xcols));
-    PLE_TRY(hipGetLastError());
-    return 0;
-  }
-  const int h = 64 * ((nr + 127) / 128);
-  if (!upper) {
-    PLE_RC(trsm(A, tr, tc, h, B, xr, xc, xcols, false, s));
-    gf2_dmat C = win(B, xr + h, xc, nr - h, xcols), L = win(A, tr + h, tc, nr - h, h), X = win(B, xr, xc, h, xcols);
-    PLE_RC(gf2_mul_dev(&C, &L, &X, 1, 0, 0, s));
-    return trsm(A, tr + h, tc + h, nr - h, B, xr + h, xc, xcols, false, s);
-  }
-  PLE_RC(trsm(A, tr + h, tc + h, nr - h, B, xr + h, xc, xcols, true, s));
-  gf2_dmat C = win(B, xr, xc, h, xcols), U = win(A, tr, tc + h, h, nr - h), X = win(B, xr + h, xc, nr - h, xcols);
-  PLE_RC(gf2_mul_dev(&C, &U, &X, 1, 0, 0, s));
-  return trsm(A, tr, tc, h, B, xr, xc, xcols, true, s);
-}
-
 struct PleCtx {
   gf2_dmat A;
   int m, n;
@@ -408,7 +336,8 @@ int ple_rec(PleCtx &c, int r0, int c0, int c1, int depth, int *rank) {
   gf2_dmat R = win(c.A, r0, cmid, cnt, c1 - cmid);
   PLE_RC(gather_rows(R, st + r0, cnt, words_of(c1 - cmid), last_mask(c1 - cmid), c.scratch, c.s));
   if (r1 > 0) {
-    PLE_RC(trsm(c.A, r0, c0, r1, c.A, r0, cmid, c1 - cmid, false, c.s));  // E12 = L11^-1 A12
+    gf2_dmat L11 = win(c.A, r0, c0, r1, r1), A12 = win(c.A, r0, cmid, r1, c1 - cmid);
+    PLE_RC(gf2_trsm_dev(&L11, &A12, 0, 0, c.s));  // E12 = L11^-1 A12
     if (cnt > r1) {
       gf2_dmat C = win(c.A, r0 + r1, cmid, cnt - r1, c1 - cmid), L = win(c.A, r0 + r1, c0, cnt - r1, r1),
                E = win(c.A, r0, cmid, r1, c1 - cmid);
@@ -602,9 +531,10 @@ extern "C" int gf2_pluq_solve_left_dev(gf2_dmat const *A, int rank, const int *P
   const u64 bmask = last_mask(kb);
   gf2_dmat Bm = win(*B, 0, 0, m, kb);
   PLE_RC(apply_rows(Bm, perm_map(P, m, m, false), s));                  // P B
-  PLE_RC(trsm(*A, 0, 0, rank, *B, 0, 0, kb, false, s));                  // Y = L11^-1 (P B)[0, r)
+  gf2_dmat T11 = win(*A, 0, 0, rank, rank), Y = win(*B, 0, 0, rank, kb);  // L11 and U11 share the block: gf2_trsm_dev reads one strict triangle
+  PLE_RC(gf2_trsm_dev(&T11, &Y, 0, 0, s));                               // Y = L11^-1 (P B)[0, r)
   if (check && rank < m) {
-    gf2_dmat C = win(*B, rank, 0, m - rank, kb), L = win(*A, rank, 0, m - rank, rank), Y = win(*B, 0, 0, rank, kb);
+    gf2_dmat C = win(*B, rank, 0, m - rank, kb), L = win(*A, rank, 0, m - rank, rank);
     if (rank > 0) PLE_RC(gf2_mul_dev(&C, &L, &Y, 1, 0, 0, s));          // rows r.. of P B minus L21 Y: zero iff consistent
     DBuf flag;
     PLE_RC(flag.alloc(sizeof(int)));
@@ -615,19 +545,7 @@ extern "C" int gf2_pluq_solve_left_dev(gf2_dmat const *A, int rank, const int *P
     PLE_TRY(hipStreamSynchronize(s));
     *inconsistent = h != 0;
   }
-  if (rank > 0) {  // U11 copied without the bits right of column r (the U12 of a recursive solve must end there)
-    const int rw = words_of(rank);
-    const long long uld = even_ld(rw);
-    DBuf ub;
-    PLE_RC(ub.alloc((size_t)rank * uld * 8));
-    PLE_TRY(hipMemsetAsync(ub.p, 0, (size_t)rank * uld * 8, s));
-    hipLaunchKernelGGL(ple_gather, dim3(grid_of((long long)rank * rw, 256)), dim3(256), 0, s, ub.as<u64>(), uld,
-                       static_cast<const u64 *>(A->data), A->ld, (const int *)nullptr, rank, rw, last_mask(rank));
-    PLE_TRY(hipGetLastError());
-    gf2_dmat U{ub.as<u64>(), uld, rank, rank};
-    PLE_RC(trsm(U, 0, 0, rank, *B, 0, 0, kb, true, s));                  // Z = U11^-1 Y, free variables 0
-    PLE_TRY(hipStreamSynchronize(s));
-  }
+  PLE_RC(gf2_trsm_dev(&T11, &Y, 1, 0, s));                               // Z = U11^-1 Y, free variables 0
   if (B->nrows > rank) {
     hipLaunchKernelGGL(ple_gather, dim3(grid_of((long long)(B->nrows - rank) * bw, 256)), dim3(256), 0, s,
                        static_cast<u64 *>(B->data) + (long long)rank * B->ld, B->ld, (const u64 *)nullptr, 0ll, (const int *)nullptr,

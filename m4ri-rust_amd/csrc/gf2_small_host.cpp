@@ -44,6 +44,7 @@ bool gf2_small_product(long long m, long long l, long long n) {
 }
 
 extern "C" long long gf2_host_small_calls(void) { return g_small_calls.load(); }
+void gf2_note_host_small_call() { g_small_calls.fetch_add(1); }
 
 // C (+)= A * B, any shapes (including windows and ragged widths).  A, B, C must not alias.
 extern "C" int gf2_mul_host_small(mzd_t *C, mzd_t const *A, mzd_t const *B, int accumulate) {

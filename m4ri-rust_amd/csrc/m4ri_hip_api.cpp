@@ -329,6 +329,8 @@ int stream_workspace(hipStream_t s, size_t bytes, void **out, int slot = 0) {
 
 }  // namespace
 
+int gf2_stream_scratch(hipStream_t s, size_t bytes, void **out, int slot) { return stream_workspace(s, bytes, out, slot); }
+
 // Give cached device memory back to the driver: waits for the device, then frees the per-stream scratch arenas (a
 // 131072^3 product leaves a 141 GiB Strassen arena behind), the deferred frees and the block cache of the current
 // device.  Safe at any quiet point; the next product allocates again.

@@ -215,6 +215,13 @@ def pluq_solve_left(A, rank, P, Q, B, check=True, stream=None):
     return not bad.value
 
 
+def trsm(T, B, upper=False, right=False, stream=None):
+    """B = T^-1 B (right=False) or B T^-1 (right=True) in place, T unit lower (upper=False) or upper triangular: only its strict
+    triangle is read.  Asynchronous on `stream`."""
+    _lib.check(_lib.lib().gf2_trsm_dev(T._on(stream), B._on(stream), int(bool(upper)), int(bool(right)), stream), "gf2_trsm_dev")
+    return B
+
+
 class Mzp:
     """Owner of an mzp_t (mzp_init / mzp_free) for tests and ctypes callers."""
 
