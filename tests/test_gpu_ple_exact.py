@@ -10,6 +10,7 @@ import pytest
 
 import gf2util as g
 from ple_cases import low_rank, structured
+from stream_util import on_stream
 
 pytestmark = pytest.mark.gpu
 
@@ -293,25 +294,6 @@ def test_apply_p_against_oracle(dev, m, n):
 
 
 # ---- calls on a caller's stream ------------------------------------------------------------------------------------------
-
-def on_stream(dev, fn_inputs, call):
-    """Queue a long sleep on a fresh stream, write the inputs there, make the call there and read the results with a torch op on
-    that stream before anything synchronises the device: a step on another stream sees unwritten inputs or unfinished work."""
-    import torch
-    s = torch.cuda.Stream()
-    staged = [torch.from_numpy(x.view(np.int64)).cuda() for x in fn_inputs]
-    torch.cuda.synchronize()
-    with torch.cuda.stream(s):
-        torch.cuda._sleep(200_000_000)  # ~0.1 s of the stream's time
-        live = [torch.empty_like(x) for x in staged]
-        for d, x in zip(live, staged):
-            d.copy_(x, non_blocking=True)
-        res = call(live, s.cuda_stream)
-        outs = [d.clone() for d in live]
-        host = [o.cpu() for o in outs]
-    del staged
-    return res, [h.numpy().view(np.uint64) for h in host]
-
 
 def test_ple_on_caller_stream(dev):
     for m, n in ((65537, 63), (4096, 4096)):
