@@ -7,6 +7,7 @@
 // mzd_mul / mzd_mul_m4rm / mzd_mul_naive exactly as `mul_impl!` selects them (binary_matrix.rs:53-95).
 #pragma once
 #include <cstdint>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -155,6 +156,14 @@ class BinMatrix {
   size_t echelonize() { return (size_t)mzd_echelonize(mzd_, 0); }  // binary_matrix.rs:254-261
   size_t rank() const { return BinMatrix(*this).echelonize(); }    // binary_matrix.rs:246-252
   BinMatrix inverted() const { return BinMatrix(mzd_inv_m4ri(nullptr, mzd_, 0)); }  // :263-268, NULL -> "Can't be NULL"
+  // null space basis K (*this * K == 0, the rows at the free columns the identity) through mzd_kernel_left_pluq on a copy; empty
+  // for full column rank.  Not part of the reference's friendly layer.
+  std::optional<BinMatrix> kernel() const {
+    BinMatrix work(*this);
+    mzd_t *k = mzd_kernel_left_pluq(work.mzd_, 0);
+    if (!k) return std::nullopt;
+    return BinMatrix(k);
+  }
   uint32_t count_ones() const {  // binary_matrix.rs:172-189
     if (!(nrows() == 1 || ncols() == 1)) throw Panic("only works on single row or single column matrices");
     uint32_t c = 0;

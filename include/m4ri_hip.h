@@ -175,6 +175,15 @@ void mzd_trsm_upper_left (mzd_t const *U, mzd_t *B, int cutoff);  /* U X = B */
 void mzd_trsm_lower_right(mzd_t const *L, mzd_t *B, int cutoff);  /* X L = B,  B k x n */
 void mzd_trsm_upper_right(mzd_t const *U, mzd_t *B, int cutoff);  /* X U = B */
 
+/* --- null space (M4RI solve.h; not declared by m4ri-sys: INTEGRATION.md gives the extern line) ---
+ * Returns K (n x (n - r), released with mzd_free) with A K = 0 for the m x n matrix A of rank r, or NULL when r == n or n == 0.  A
+ * is overwritten and left holding its reduced row echelon form E, as by mzd_solve_left; it may be a window (bits of the parent
+ * outside it do not change).  Every bit of K is defined: with the pivot columns p_0 < ... < p_{r-1} and the free columns f_0 < ... <
+ * f_{n-r-1}, row f_j of K is the unit vector e_j and row p_i holds E[i][f_j] in column j.  The order (ascending free columns) is this
+ * library's own, not the one M4RI's PLUQ recipe induces; M4RI promises only "an n x (n - r) matrix with A K = 0".  The basis comes
+ * from the reduced echelon form, not from a PLUQ factorisation; cutoff is accepted and ignored.  A device failure aborts. */
+mzd_t *mzd_kernel_left_pluq(mzd_t *A, int cutoff);
+
 /* ===================================================================================== */
 /* 2. Device-resident API                                                                 */
 /* ===================================================================================== */
@@ -241,6 +250,15 @@ int gf2_pluq_solve_left_dev(gf2_dmat const *A, int rank, const int *P, const int
  * as they are).  A non-square T or a dimension mismatch returns -1 and sets gf2_last_error; n = 0 or an empty B returns 0 without a
  * launch.  Asynchronous on `stream`, like gf2_mul_dev: one launch inverts the diagonal blocks, the rest is products. */
 int gf2_trsm_dev(gf2_dmat const *T, gf2_dmat *B, int upper, int right, void *stream);
+/* Null space of a device matrix, the contract of mzd_kernel_left_pluq above: A (may be a strided view) is reduced in place to its
+ * reduced row echelon form; *K is filled in by the call: n x (n - rank), allocated with gf2_dmat_alloc and freed by the caller with
+ * gf2_dmat_free, the excess bits of its last word zero; nullity 0: K = {NULL, 0, n, 0}, nothing allocated.  rank and pivot_cols as in
+ * gf2_echelonize_dev.  Synchronous on `stream` (the rank must reach the host before K can be sized) and ordered behind the work
+ * pending there.  Bad arguments return -1 and set gf2_last_error. */
+int gf2_nullspace_dev(gf2_dmat *A, gf2_dmat *K, int *rank, int *pivot_cols, void *stream);
+/* UNSTABLE diagnostic for tools/nullspace_bench.py, not part of the supported interface (it may change or go without notice):
+ * event-measured milliseconds of the assembly launch of this thread's last gf2_nullspace_dev that ran while gf2_prof_enable was on */
+double gf2_nullspace_last_assembly_ms(void);
 
 /* Strassen levels a product of this shape would use right now (0 = plain M4RM): the cost model's choice, lowered until the
  * operand arena of that many levels fits into free device memory (without a device: the cost model's choice) */
@@ -322,6 +340,10 @@ int gf2_ple_host_small(mzd_t *A, int pluq, int *P, int *Q);                     
 /* host routine of the size dispatch of mzd_trsm_* (work = n * n * ceil(k / 64)), exported for tests without a device; 0 on
  * success, -1 for a non-square T or a dimension mismatch */
 int gf2_trsm_host_small(mzd_t const *T, mzd_t *B, int upper, int right);
+/* host routine of the size dispatch of mzd_kernel_left_pluq (the work measure and limit of mzd_echelonize), exported for tests without
+ * a device: gf2_echelonize_host_small (which counts the run) and a word-parallel assembly.  A is left holding its reduced echelon
+ * form; *K receives the basis (mzd_free) or NULL for full column rank.  Returns the rank, -1 for a null argument. */
+int gf2_nullspace_host_small(mzd_t *A, mzd_t **K);
 long long gf2_host_small_calls(void);
 
 /* compact binary file format for host matrices ("GF2M", version, nrows, ncols, dense little-endian rows);

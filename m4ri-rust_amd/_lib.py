@@ -105,6 +105,7 @@ _PROTOS = {
     "mzd_trsm_upper_left": (None, [MzdP, MzdP, _I]),
     "mzd_trsm_lower_right": (None, [MzdP, MzdP, _I]),
     "mzd_trsm_upper_right": (None, [MzdP, MzdP, _I]),
+    "mzd_kernel_left_pluq": (MzdP, [MzdP, _I]),
     "mzd_mul_m4rm": (MzdP, [MzdP, MzdP, MzdP, _I]),
     "mzd_addmul_m4rm": (MzdP, [MzdP, MzdP, MzdP, _I]),
     "mzd_mul": (MzdP, [MzdP, MzdP, MzdP, _I]),
@@ -141,6 +142,8 @@ _PROTOS = {
     "gf2_pluq_solve_left_dev": (_I, [DMatP, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), DMatP, _I, ctypes.POINTER(_I),
                                      ctypes.c_void_p]),
     "gf2_trsm_dev": (_I, [DMatP, DMatP, _I, _I, ctypes.c_void_p]),
+    "gf2_nullspace_dev": (_I, [DMatP, DMatP, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.c_void_p]),
+    "gf2_nullspace_last_assembly_ms": (ctypes.c_double, []),
     "gf2_mul_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I, _I, _I]),
     "gf2_mul_multi": (MzdP, [MzdP, MzdP, MzdP, _I, _I, ctypes.POINTER(_I), _I]),
     "gf2_mzd_cache_on_device": (_I, [MzdP]),
@@ -153,6 +156,7 @@ _PROTOS = {
     "gf2_echelonize_host_small": (_I, [MzdP, _I]),
     "gf2_ple_host_small": (_I, [MzdP, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "gf2_trsm_host_small": (_I, [MzdP, MzdP, _I, _I]),
+    "gf2_nullspace_host_small": (_I, [MzdP, ctypes.POINTER(MzdP)]),
     "gf2_host_small_calls": (ctypes.c_longlong, []),
     "gf2_mzd_save": (_I, [ctypes.c_char_p, MzdP]),
     "gf2_mzd_load": (MzdP, [ctypes.c_char_p]),

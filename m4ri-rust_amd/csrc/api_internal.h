@@ -28,3 +28,13 @@ int gf2_fail_hip(hipError_t e, const char *what);
 int gf2_stream_scratch(hipStream_t s, size_t bytes, void **out, int slot);
 // counts a run of a host routine of the size dispatch (gf2_host_small_calls)
 void gf2_note_host_small_call();
+// pooled device memory of m4ri_hip_api.cpp for the other translation units (gf2_nullspace.hip).  gf2_dev_free is not stream-ordered: the
+// caller has synchronised every stream that touched the block
+int gf2_dev_alloc(void **p, size_t bytes);
+void gf2_dev_free(void *p, size_t bytes);
+// the reduced row echelon form of gf2_echelonize_dev(full = 1, all columns) that also hands over the elimination's device array of pivot
+// columns: *pivcols_dev (null when the matrix is empty) is released with gf2_dev_free(*pivcols_dev, *pivcols_bytes); pivcols_host may
+// be null.  Synchronous on s.
+int gf2_rref_keep_pivots_dev(gf2_dmat *A, int *rank, int *pivcols_host, void **pivcols_dev, size_t *pivcols_bytes, hipStream_t s);
+// gf2_prof_enable's switch (gf2_nullspace.hip times its assembly launch while it is on)
+bool gf2_prof_is_on();

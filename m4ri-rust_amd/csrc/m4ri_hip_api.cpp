@@ -330,6 +330,8 @@ int stream_workspace(hipStream_t s, size_t bytes, void **out, int slot = 0) {
 }  // namespace
 
 int gf2_stream_scratch(hipStream_t s, size_t bytes, void **out, int slot) { return stream_workspace(s, bytes, out, slot); }
+int gf2_dev_alloc(void **p, size_t bytes) { return dev_alloc(p, bytes); }
+void gf2_dev_free(void *p, size_t bytes) { dev_free(p, bytes); }
 
 // Give cached device memory back to the driver: waits for the device, then frees the per-stream scratch arenas (a
 // 131072^3 product leaves a 141 GiB Strassen arena behind), the deferred frees and the block cache of the current
@@ -402,6 +404,11 @@ std::vector<ProfPair> g_prof;
 extern "C" void gf2_prof_enable(int on) {
   std::lock_guard<std::mutex> lk(g_prof_mu);
   g_prof_on = on != 0;
+}
+
+bool gf2_prof_is_on() {
+  std::lock_guard<std::mutex> lk(g_prof_mu);
+  return g_prof_on;
 }
 
 extern "C" int gf2_prof_read(int *launches, double *ms, int reset) {
@@ -3108,6 +3115,16 @@ extern "C" int gf2_echelonize_dev(gf2_dmat *A, int full, int ncols_limit, int *r
   if (int rc = get_stream(stream, &s)) return rc;
   std::lock_guard<std::mutex> lk(g_enqueue_mu);
   return echelonize_dev(A, full, ncols_limit, rank, pivot_cols, nullptr, s);
+}
+
+int gf2_rref_keep_pivots_dev(gf2_dmat *A, int *rank, int *pivcols_host, void **pivcols_dev, size_t *pivcols_bytes, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(g_enqueue_mu);
+  DevBuf pivs;
+  if (int rc = echelonize_dev(A, 1, 0, rank, pivcols_host, &pivs, s)) return rc;
+  *pivcols_dev = pivs.p;  // ownership moves to the caller
+  *pivcols_bytes = pivs.bytes;
+  pivs.p = nullptr;
+  return 0;
 }
 
 // [ A | 0-pad to a word boundary | I ] -> reduced echelon form of the left part; singular unless rank == n

@@ -116,6 +116,10 @@ class DMat:
     def rank(self):
         return echelonize(self.clone(), full=False)[0]
 
+    def kernel(self):
+        """Null space basis K (self * K = 0) as a new DMat, or None for full column rank; self is left unchanged."""
+        return nullspace(self.clone())[0]
+
     def inverted(self):
         inv = inverse(self)
         if inv is None:
@@ -176,6 +180,21 @@ def inverse(A, stream=None):
     _lib.check(_lib.lib().gf2_inverse_dev(out._on(stream), A._on(stream), ctypes.byref(singular), stream),
                "gf2_inverse_dev")
     return None if singular.value else out
+
+
+def nullspace(A, stream=None):
+    """A is reduced in place to its reduced row echelon form -> (K or None, rank, pivot columns): K is n x (n - rank) with A K = 0,
+    its rows at the free columns the identity (ascending free columns); None when the rank is n.  Synchronous on `stream`."""
+    rank = ctypes.c_int(0)
+    piv = (ctypes.c_int * max(min(A.nrows, A.ncols), 1))()
+    ks = DMatStruct()
+    _lib.check(_lib.lib().gf2_nullspace_dev(A._on(stream), ctypes.byref(ks), ctypes.byref(rank), piv, stream), "gf2_nullspace_dev")
+    K = None
+    if ks.data:
+        K = DMat.wrap(ks.data, ks.nrows, ks.ncols, ks.ld)
+        K._owned = True  # allocated by the library for the caller: released like a matrix of DMat's own
+        K._streams.add(stream)
+    return K, rank.value, list(piv[:rank.value])
 
 
 def prof_enable(on):

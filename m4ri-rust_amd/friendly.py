@@ -369,6 +369,12 @@ class BinMatrix:
             raise PanicError("Can't be NULL")
         return BinMatrix(ptr)
 
+    def kernel(self):
+        """Null space basis K (self * K = 0, n x (n - rank), the rows at the free columns the identity) through
+        mzd_kernel_left_pluq on a copy, or None for full column rank."""
+        ptr = _lib.lib().mzd_kernel_left_pluq(self.clone().mzd, 0)
+        return BinMatrix(ptr) if ptr else None
+
     # -- products --
     def mul_slice(self, other):
         """A * v^T with v given as u64 words (binary_matrix.rs:416-431): always mzd_mul_naive."""
