@@ -228,6 +228,24 @@ int gf2_mul_nt_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *Bt, int accum
 int gf2_add_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *B, void *stream);
 int gf2_transpose_dev(gf2_dmat *D, gf2_dmat const *S, void *stream);
 int gf2_equal_dev(gf2_dmat const *A, gf2_dmat const *B, int *equal, void *stream);
+/* Assembly on the device.  The four calls below move bits between ANY bit offsets; destinations are caller-allocated and may be views in
+ * a larger buffer.  Every argument is checked before the first HIP call: a destination of the wrong shape, a rectangle that leaves S or
+ * D, a negative argument or a null pointer returns -1 and sets gf2_last_error; an empty rectangle returns 0 without a launch.  S and D
+ * may be views of one buffer as long as no bit belongs to both rectangles (two column ranges of one parent): with equal `ld` the
+ * rectangles are compared exactly, with different `ld` any intersection of their address ranges is refused; overlapping rectangles
+ * return -1 (no in-place shift).  Unlike the calls above, these accept views whose rows are only 8-byte aligned (odd `ld`).
+ * Asynchronous on `stream`, like gf2_mul_dev. */
+/* D[dr+i][dc+j] (^)= S[sr+i][sc+j], i < nrows, j < ncols: any bit offsets. Only the rectangle's bits of D change. */
+int gf2_copy_block_dev(gf2_dmat *D, int dr, int dc, gf2_dmat const *S, int sr, int sc, int nrows, int ncols,
+                       int accumulate, void *stream);
+/* The three below write D / C as a whole matrix: the excess bits of its last word come out zero whatever it held before (a fresh
+ * gf2_dmat_alloc block will do), and a view keeps its neighbours. */
+/* mzd_submatrix (mzd.rs:205-212): D = S[lowr:highr, lowc:highc]; D must be (highr-lowr) x (highc-lowc) */
+int gf2_submatrix_dev(gf2_dmat *D, gf2_dmat const *S, int lowr, int lowc, int highr, int highc, void *stream);
+/* mzd_concat (mzd.rs:195): C = [A | B], equal row counts, C is A.nrows x (A.ncols + B.ncols); C may alias neither A nor B */
+int gf2_concat_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *B, void *stream);
+/* mzd_stack (mzd.rs:201): C = [A ; B], equal column counts */
+int gf2_stack_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *B, void *stream);
 
 /* In-place echelon form of the first ncols_limit columns (0 = all) of a device matrix; the remaining columns follow
  * the row operations (augmented systems).  *rank receives the rank, pivot_cols (host, may be NULL, >= min(rows, limit)
@@ -235,6 +253,13 @@ int gf2_equal_dev(gf2_dmat const *A, gf2_dmat const *B, int *equal, void *stream
 int gf2_echelonize_dev(gf2_dmat *A, int full, int ncols_limit, int *rank, int *pivot_cols, void *stream);
 /* Ainv = A^-1 for square A; *singular = 1 (Ainv untouched) if A has no inverse.  Synchronous. */
 int gf2_inverse_dev(gf2_dmat *Ainv, gf2_dmat const *A, int *singular, void *stream);
+/* mzd_solve_left's contract on device matrices: A is m x n, B has >= max(m, n) rows and holds the right-hand
+ * side in its first m rows; on return A holds its reduced row echelon form, rows 0 .. n-1 of B hold X (free variables 0) and every
+ * further row of B is zero; *inconsistent = 1 when check != 0 and the system has no solution (B is then as mzd_solve_left leaves it).
+ * A and B may be strided views: bits outside them do not change.  m, n or B.ncols equal to 0: returns 0, nothing is done.  A shape
+ * error returns -1 and sets gf2_last_error (the host entry aborts instead).  Synchronous on `stream` (the rank must reach the host)
+ * and ordered behind the work pending there. */
+int gf2_solve_left_dev(gf2_dmat *A, gf2_dmat *B, int check, int *inconsistent, void *stream);
 /* PLE (pluq = 0) or PLUQ (pluq = 1) of a device matrix in place, the layout of mzd_ple / mzd_pluq; P (nrows ints) and Q (ncols
  * ints) are HOST arrays that receive the transposition lists.  Synchronous. */
 int gf2_ple_dev(gf2_dmat *A, int pluq, int *P, int *Q, int *rank, void *stream);

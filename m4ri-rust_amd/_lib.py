@@ -135,6 +135,11 @@ _PROTOS = {
     "gf2_add_dev": (_I, [DMatP, DMatP, DMatP, ctypes.c_void_p]),
     "gf2_transpose_dev": (_I, [DMatP, DMatP, ctypes.c_void_p]),
     "gf2_equal_dev": (_I, [DMatP, DMatP, ctypes.POINTER(_I), ctypes.c_void_p]),
+    "gf2_copy_block_dev": (_I, [DMatP, _I, _I, DMatP, _I, _I, _I, _I, _I, ctypes.c_void_p]),
+    "gf2_submatrix_dev": (_I, [DMatP, DMatP, _I, _I, _I, _I, ctypes.c_void_p]),
+    "gf2_concat_dev": (_I, [DMatP, DMatP, DMatP, ctypes.c_void_p]),
+    "gf2_stack_dev": (_I, [DMatP, DMatP, DMatP, ctypes.c_void_p]),
+    "gf2_solve_left_dev": (_I, [DMatP, DMatP, _I, ctypes.POINTER(_I), ctypes.c_void_p]),
     "gf2_echelonize_dev": (_I, [DMatP, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.c_void_p]),
     "gf2_inverse_dev": (_I, [DMatP, DMatP, ctypes.POINTER(_I), ctypes.c_void_p]),
     "gf2_ple_dev": (_I, [DMatP, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.c_void_p]),

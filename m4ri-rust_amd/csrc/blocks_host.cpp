@@ -1,0 +1,131 @@
+// blocks_host.cpp -- device-resident block copy, submatrix, concat and stack (include/m4ri_hip.h section 2; kernel: gf2_blocks.hip;
+// DESIGN.md section 7.5).  Every argument is checked before the first HIP call, so a bad call fails the same way with and without a
+// device, and an empty rectangle returns without one.
+#include <stdint.h>
+
+#include <string>
+
+#include "api_internal.h"
+#include "gf2_kernels.h"
+
+namespace {
+
+inline long long words_of(long long bits) { return (bits + 63) >> 6; }
+
+int bad(const char *fn, const char *what) { return gf2_fail_msg((std::string(fn) + ": " + what).c_str()); }
+
+// a matrix argument that can be addressed: `name` goes into the message
+int check_mat(const char *fn, const char *name, gf2_dmat const *M) {
+  if (!M) return bad(fn, (std::string(name) + " is null").c_str());
+  if (M->nrows < 0 || M->ncols < 0) return bad(fn, (std::string(name) + " has a negative dimension").c_str());
+  if (M->nrows > 0 && M->ncols > 0) {
+    if (!M->data) return bad(fn, (std::string(name) + ".data is null").c_str());
+    if (reinterpret_cast<uintptr_t>(M->data) & 7) return bad(fn, (std::string(name) + ".data is not 8-byte aligned").c_str());
+    if (M->ld < words_of(M->ncols)) return bad(fn, (std::string(name) + ".ld is smaller than the row width").c_str());
+  }
+  return 0;
+}
+
+// Do the rectangles share a bit?  (Both are non-empty and lie inside their matrices.)  With one row stride a bit's address is
+// row * L + column (L = 64 * ld), whatever parent the two views were cut from, so the answer is exact: row i of S's rectangle is the
+// interval [i L, i L + ncols), row j of D's the interval [x + j L, x + j L + ncols) with x the distance of the rectangles' first
+// bits, and ncols <= L.  With different strides the word ranges of the two rectangles are compared: conservative.
+bool rects_overlap(gf2_dmat const *D, long long dr, long long dc, gf2_dmat const *S, long long sr, long long sc, long long nrows,
+                   long long ncols) {
+  const __int128 s0 = (__int128)reinterpret_cast<uintptr_t>(S->data) * 8 + ((__int128)sr * S->ld) * 64 + sc;
+  const __int128 d0 = (__int128)reinterpret_cast<uintptr_t>(D->data) * 8 + ((__int128)dr * D->ld) * 64 + dc;
+  if (S->ld == D->ld) {
+    const __int128 L = (__int128)S->ld * 64, x = d0 - s0;
+    __int128 e = x / L, f = x % L;
+    if (f < 0) {
+      f += L;
+      e -= 1;
+    }
+    // D's row j meets S's row i = j + e (distance f) or i = j + e + 1 (distance L - f)
+    const bool same = (e < nrows && -e < nrows) && f < ncols;
+    const bool next = (e + 1 < nrows && -(e + 1) < nrows) && L - f < ncols;
+    return same || next;
+  }
+  const __int128 s1 = s0 + ((__int128)(nrows - 1) * S->ld) * 64 + ncols - 1, d1 = d0 + ((__int128)(nrows - 1) * D->ld) * 64 + ncols - 1;
+  return (s0 >> 6) <= (d1 >> 6) && (d0 >> 6) <= (s1 >> 6);
+}
+
+// 0: go ahead; 1: nothing to do; -1: refused (gf2_last_error is set)
+int check_block(const char *fn, gf2_dmat const *D, int dr, int dc, gf2_dmat const *S, int sr, int sc, int nrows, int ncols) {
+  if (check_mat(fn, "D", D) || check_mat(fn, "S", S)) return -1;
+  if (dr < 0 || dc < 0 || sr < 0 || sc < 0 || nrows < 0 || ncols < 0) {
+    const char *name = dr < 0 ? "dr" : dc < 0 ? "dc" : sr < 0 ? "sr" : sc < 0 ? "sc" : nrows < 0 ? "nrows" : "ncols";
+    return bad(fn, (std::string(name) + " is negative").c_str());
+  }
+  if ((long long)sr + nrows > S->nrows || (long long)sc + ncols > S->ncols) return bad(fn, "the rectangle leaves S");
+  if ((long long)dr + nrows > D->nrows || (long long)dc + ncols > D->ncols) return bad(fn, "the rectangle leaves D");
+  if (nrows == 0 || ncols == 0) return 1;
+  if (rects_overlap(D, dr, dc, S, sr, sc, nrows, ncols))
+    return bad(fn, "the rectangles of S and D overlap (or, with different ld, their address ranges do)");
+  return 0;
+}
+
+// whole_matrix: the call writes D as a matrix (submatrix, concat, stack), so where it writes D's last column it also leaves the excess
+// bits of that word zero, whatever D held before (a fresh gf2_dmat_alloc block is not cleared)
+int launch(const char *fn, gf2_dmat *D, int dr, int dc, gf2_dmat const *S, int sr, int sc, int nrows, int ncols, int accumulate,
+           bool whole_matrix, void *stream) {
+  const int zero_tail = whole_matrix && dc + ncols == D->ncols;
+  hipError_t e = gf2k_copy_block(D->data, D->ld, dr, dc, S->data, S->ld, sr, sc, nrows, ncols, accumulate, zero_tail,
+                                 static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+}
+
+int no_device(const char *fn) { return gf2_device_count() > 0 ? 0 : bad(fn, "no usable HIP device"); }
+
+}  // namespace
+
+extern "C" int gf2_copy_block_dev(gf2_dmat *D, int dr, int dc, gf2_dmat const *S, int sr, int sc, int nrows, int ncols, int accumulate,
+                                  void *stream) {
+  static const char fn[] = "gf2_copy_block_dev";
+  if (int rc = check_block(fn, D, dr, dc, S, sr, sc, nrows, ncols)) return rc < 0 ? rc : 0;
+  if (int rc = no_device(fn)) return rc;
+  return launch(fn, D, dr, dc, S, sr, sc, nrows, ncols, accumulate, false, stream);
+}
+
+extern "C" int gf2_submatrix_dev(gf2_dmat *D, gf2_dmat const *S, int lowr, int lowc, int highr, int highc, void *stream) {
+  static const char fn[] = "gf2_submatrix_dev";
+  if (check_mat(fn, "D", D) || check_mat(fn, "S", S)) return -1;
+  if (lowr < 0 || lowc < 0 || highr < lowr || highc < lowc) return bad(fn, "lowr / lowc / highr / highc do not describe a rectangle");
+  if (D->nrows != highr - lowr || D->ncols != highc - lowc) return bad(fn, "D must be (highr - lowr) x (highc - lowc)");
+  if (int rc = check_block(fn, D, 0, 0, S, lowr, lowc, highr - lowr, highc - lowc)) return rc < 0 ? rc : 0;
+  if (int rc = no_device(fn)) return rc;
+  return launch(fn, D, 0, 0, S, lowr, lowc, highr - lowr, highc - lowc, 0, true, stream);
+}
+
+// two copies into one destination, both checked before the first is enqueued
+static int two_blocks(const char *fn, gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *B, int br, int bc, void *stream) {
+  const int ca = check_block(fn, C, 0, 0, A, 0, 0, A->nrows, A->ncols);
+  if (ca < 0) return ca;
+  const int cb = check_block(fn, C, br, bc, B, 0, 0, B->nrows, B->ncols);
+  if (cb < 0) return cb;
+  if (ca && cb) return 0;
+  if (int rc = no_device(fn)) return rc;
+  if (!ca)
+    if (int rc = launch(fn, C, 0, 0, A, 0, 0, A->nrows, A->ncols, 0, true, stream)) return rc;
+  if (!cb)
+    if (int rc = launch(fn, C, br, bc, B, 0, 0, B->nrows, B->ncols, 0, true, stream)) return rc;
+  return 0;
+}
+
+extern "C" int gf2_concat_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *B, void *stream) {
+  static const char fn[] = "gf2_concat_dev";
+  if (check_mat(fn, "C", C) || check_mat(fn, "A", A) || check_mat(fn, "B", B)) return -1;
+  if (A->nrows != B->nrows) return bad(fn, "A and B must have equal row counts (A.nrows != B.nrows)");
+  if (C->nrows != A->nrows || (long long)C->ncols != (long long)A->ncols + B->ncols)
+    return bad(fn, "C must be A.nrows x (A.ncols + B.ncols)");
+  return two_blocks(fn, C, A, B, 0, A->ncols, stream);
+}
+
+extern "C" int gf2_stack_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *B, void *stream) {
+  static const char fn[] = "gf2_stack_dev";
+  if (check_mat(fn, "C", C) || check_mat(fn, "A", A) || check_mat(fn, "B", B)) return -1;
+  if (A->ncols != B->ncols) return bad(fn, "A and B must have equal column counts (A.ncols != B.ncols)");
+  if ((long long)C->nrows != (long long)A->nrows + B->nrows || C->ncols != A->ncols)
+    return bad(fn, "C must be (A.nrows + B.nrows) x A.ncols");
+  return two_blocks(fn, C, A, B, A->nrows, 0, stream);
+}

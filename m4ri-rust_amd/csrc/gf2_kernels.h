@@ -111,6 +111,10 @@ hipError_t gf2k_xor2d(uint64_t *C, long long ldc, const uint64_t *A, long long l
                       int rows, int words, hipStream_t stream);
 hipError_t gf2k_padcopy(uint64_t *dst, long long ldd, int drows, int dwords, const uint64_t *src, long long lds_, int srows,
                         int scols, hipStream_t stream);  // scols: the source's columns (its last word is masked)
+// D[dr + i][dc + j] (^)= S[sr + i][sc + j], i < nrows, j < ncols, any bit offsets (gf2_blocks.hip); only the rectangle's bits of D
+// change -- and, with zero_tail, the bits above the rectangle's last column in the last destination word of each row (cleared)
+hipError_t gf2k_copy_block(uint64_t *D, long long ldd, long long dr, long long dc, const uint64_t *S, long long lds_, long long sr,
+                           long long sc, int nrows, int ncols, int accumulate, int zero_tail, hipStream_t stream);
 hipError_t gf2k_fill_random(uint64_t *M, long long ld, int rows, int cols, uint64_t seed, long long row0, long long fullw,
                             long long colw0, hipStream_t stream);
 hipError_t gf2k_diff(const uint64_t *A, long long lda, const uint64_t *B, long long ldb, int rows, int cols, int *diff,

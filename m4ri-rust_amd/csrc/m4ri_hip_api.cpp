@@ -3300,3 +3300,68 @@ extern "C" int mzd_solve_left(mzd_t *A, mzd_t *B, int cutoff, int inconsistency_
   }
   return inconsistent ? -1 : 0;
 }
+
+// mzd_solve_left on device matrices: the same steps, with both uploads and the download of A replaced by block copies on the device
+// and the solution rows scattered straight into B.
+extern "C" int gf2_solve_left_dev(gf2_dmat *A, gf2_dmat *B, int check, int *inconsistent, void *stream) {
+  if (!A || !B || !inconsistent) return fail_msg("gf2_solve_left_dev: null argument (A, B or inconsistent)");
+  if (A->nrows < 0 || A->ncols < 0 || B->nrows < 0 || B->ncols < 0) return fail_msg("gf2_solve_left_dev: negative dimension");
+  if (A->ncols > B->nrows) return fail_msg("gf2_solve_left_dev: A.ncols must not exceed B.nrows");
+  if (A->nrows > B->nrows) return fail_msg("gf2_solve_left_dev: A.nrows must not exceed B.nrows");
+  *inconsistent = 0;
+  const int m = A->nrows, n = A->ncols, kb = B->ncols;
+  if (m == 0 || n == 0 || kb == 0) return 0;
+  if (!A->data || !B->data) return fail_msg("gf2_solve_left_dev: null argument (A.data or B.data)");
+  const int nw = words_of(n), bw = words_of(kb);
+  if (A->ld < nw || B->ld < bw) return fail_msg("gf2_solve_left_dev: row stride (A.ld or B.ld) smaller than row width");
+  if ((long long)nw * 64 + kb > INT32_MAX) return fail_msg("gf2_solve_left_dev: A.ncols + B.ncols is too large");
+  if (int rc = require_device()) return rc;
+  hipStream_t s;
+  if (int rc = get_stream(stream, &s)) return rc;
+  std::lock_guard<std::mutex> lk(g_enqueue_mu);
+  int rc = 0;
+  {
+    // T = [ A | pad | B[0:m] ]
+    gf2_dmat T{nullptr, dev_ld_for(nw * 64 + kb), m, nw * 64 + kb};
+    DevBuf tb, flag, pivs;
+    do {
+      if ((rc = tb.alloc((size_t)m * T.ld * sizeof(u64)))) break;
+      T.data = tb.as<u64>();
+      hipError_t e = hipMemsetAsync(T.data, 0, (size_t)m * T.ld * sizeof(u64), s);
+      if (e != hipSuccess) {
+        rc = fail(e, "gf2_solve_left_dev: clearing the augmented matrix");
+        break;
+      }
+      if ((rc = gf2_copy_block_dev(&T, 0, 0, A, 0, 0, m, n, 0, s))) break;
+      if ((rc = gf2_copy_block_dev(&T, 0, nw * 64, B, 0, 0, m, kb, 0, s))) break;
+      int rank = 0;
+      if ((rc = echelonize_dev(&T, 1, n, &rank, nullptr, &pivs, s))) break;
+      if (check && rank < m) {
+        int host = 0;
+        if ((rc = flag.alloc(sizeof(int)))) break;
+        e = hipMemsetAsync(flag.p, 0, sizeof(int), s);
+        if (e == hipSuccess) e = gf2k_any_nonzero(T.data + nw, T.ld, rank, m, kb, flag.as<int>(), s);
+        if (e == hipSuccess) e = hipMemcpyAsync(&host, flag.p, sizeof(int), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+          rc = fail(e, "gf2_solve_left_dev: consistency check");
+          break;
+        }
+        *inconsistent = host ? 1 : 0;
+      }
+      // X[pivot column k] = reduced right-hand side row k; free variables are 0; every other row of B is cleared.  Whole words: the
+      // excess bits of B's last word are zero before (a valid gf2_dmat) and after (T's are)
+      e = gf2k_xor2d(B->data, B->ld, nullptr, 0, nullptr, 0, B->nrows, bw, s);
+      if (e == hipSuccess) e = gf2k_scatter_rows(B->data, B->ld, T.data + nw, T.ld, bw, pivs.as<int>(), rank, s);
+      if (e != hipSuccess) {
+        rc = fail(e, "gf2_solve_left_dev: solution rows");
+        break;
+      }
+      gf2_dmat Ared{T.data, T.ld, m, n};  // A is left holding its reduced echelon form
+      if ((rc = gf2_copy_block_dev(A, 0, 0, &Ared, 0, 0, m, n, 0, s))) break;
+    } while (0);
+    // the scratch goes back to the pool when this block ends: nothing queued may still use it
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail(hipGetLastError(), "gf2_solve_left_dev: hipStreamSynchronize");
+  }
+  return rc;
+}

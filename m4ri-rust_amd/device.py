@@ -126,6 +126,23 @@ class DMat:
             raise _lib.HipError("matrix is singular")
         return inv
 
+    # -- binary_matrix.rs: augmented / stacked / get_window / set_window, on the device --
+    def augmented(self, other):
+        """[self | other] as a new DMat."""
+        return concat(self, other)
+
+    def stacked(self, other):
+        """[self ; other] as a new DMat."""
+        return stack(self, other)
+
+    def get_window(self, start_row, start_col, high_row, high_col):
+        """Rows [start_row, high_row) x columns [start_col, high_col) as a new DMat."""
+        return submatrix(self, start_row, start_col, high_row, high_col)
+
+    def set_window(self, start_row, start_col, other):
+        """Overwrite the block of other's shape at (start_row, start_col) with other."""
+        copy_block(self, start_row, start_col, other, 0, 0, other.nrows, other.ncols)
+
 
 def mul(A, B, C=None, accumulate=False, algo="auto", param=0, stream=None):
     """C (+)= A*B on the device; asynchronous on `stream` (int hipStream_t or None)."""
@@ -155,6 +172,38 @@ def transpose(S, D=None, stream=None):
         D = DMat(S.ncols, S.nrows)
     _lib.check(_lib.lib().gf2_transpose_dev(D._on(stream), S._on(stream), stream), "gf2_transpose_dev")
     return D
+
+
+def copy_block(D, dr, dc, S, sr, sc, nrows, ncols, accumulate=False, stream=None):
+    """D[dr+i][dc+j] (^)= S[sr+i][sc+j] for i < nrows, j < ncols, at any bit offsets; only those bits of D change.  S and D may share
+    a buffer when the rectangles do not overlap.  Asynchronous on `stream`."""
+    _lib.check(_lib.lib().gf2_copy_block_dev(D._on(stream), dr, dc, S._on(stream), sr, sc, nrows, ncols, int(bool(accumulate)),
+                                             stream), "gf2_copy_block_dev")
+    return D
+
+
+def submatrix(S, lowr, lowc, highr, highc, D=None, stream=None):
+    """D = S[lowr:highr, lowc:highc] (mzd_submatrix)."""
+    if D is None:
+        D = DMat(highr - lowr, highc - lowc)
+    _lib.check(_lib.lib().gf2_submatrix_dev(D._on(stream), S._on(stream), lowr, lowc, highr, highc, stream), "gf2_submatrix_dev")
+    return D
+
+
+def concat(A, B, C=None, stream=None):
+    """C = [A | B] (mzd_concat)."""
+    if C is None:
+        C = DMat(A.nrows, A.ncols + B.ncols)
+    _lib.check(_lib.lib().gf2_concat_dev(C._on(stream), A._on(stream), B._on(stream), stream), "gf2_concat_dev")
+    return C
+
+
+def stack(A, B, C=None, stream=None):
+    """C = [A ; B] (mzd_stack)."""
+    if C is None:
+        C = DMat(A.nrows + B.nrows, A.ncols)
+    _lib.check(_lib.lib().gf2_stack_dev(C._on(stream), A._on(stream), B._on(stream), stream), "gf2_stack_dev")
+    return C
 
 
 def equal(A, B, stream=None):
@@ -231,6 +280,15 @@ def pluq_solve_left(A, rank, P, Q, B, check=True, stream=None):
     bad = ctypes.c_int(0)
     _lib.check(_lib.lib().gf2_pluq_solve_left_dev(A._on(stream), rank, pa, qa, B._on(stream), int(bool(check)),
                                                   ctypes.byref(bad), stream), "gf2_pluq_solve_left_dev")
+    return not bad.value
+
+
+def solve_left(A, B, check=True, stream=None):
+    """Solve A X = B in place (mzd_solve_left's contract): A is left holding its reduced row echelon form, rows 0 .. A.ncols-1 of B hold
+    X (free variables 0), further rows are zero -> False if check finds the system inconsistent.  Synchronous on `stream`."""
+    bad = ctypes.c_int(0)
+    _lib.check(_lib.lib().gf2_solve_left_dev(A._on(stream), B._on(stream), int(bool(check)), ctypes.byref(bad), stream),
+               "gf2_solve_left_dev")
     return not bad.value
 
 
