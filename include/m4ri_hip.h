@@ -253,6 +253,25 @@ int gf2_stack_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *B, void *strea
 int gf2_echelonize_dev(gf2_dmat *A, int full, int ncols_limit, int *rank, int *pivot_cols, void *stream);
 /* Ainv = A^-1 for square A; *singular = 1 (Ainv untouched) if A has no inverse.  Synchronous. */
 int gf2_inverse_dev(gf2_dmat *Ainv, gf2_dmat const *A, int *singular, void *stream);
+/* --- batched elimination of small matrices (contract per matrix: INTEGRATION.md section 3) ---
+ * A batch is `batch` matrices of equal shape stored one below the other in one gf2_dmat: matrix b is rows [b*m, (b+1)*m), so
+ * gf2_concat_dev of two stacks is the stack of [A_b | B_b].  Limits: 1 <= m <= 512 rows and 1 <= ncols <= 1024 columns per matrix;
+ * a larger shape returns -1 and says so in gf2_last_error (such callers have gf2_echelonize_dev).  A->nrows % m != 0, a null `data`,
+ * ld < ceil(ncols / 64) and a negative m or ncols_limit return -1 as well.  Every argument is checked before a device is required;
+ * A->nrows == 0 returns 0 without a launch.  A stack may be a strided view: only the ceil(ncols / 64) words of each row are read and
+ * written.  Both calls are one launch on `stream`, asynchronous like gf2_mul_dev: no host synchronisation, no allocation. */
+/* every matrix of the stack A is replaced by its echelon form, with the contract of gf2_echelonize_dev(full, ncols_limit).  ranks and
+ * pivot_cols are DEVICE arrays, either may be NULL: ranks[b] is the rank of matrix b; pivot_cols[b * P + i], P = min(m, limit), is its
+ * i-th pivot column for i < ranks[b] and -1 beyond. */
+int gf2_echelonize_batch_dev(gf2_dmat *A, int m, int full, int ncols_limit, int *ranks, int *pivot_cols, void *stream);
+/* block b of Ainv = (block b of A)^-1 for the n x n blocks (n <= 512) of the stacks A and Ainv; singular[b] (DEVICE, may be NULL) = 1
+ * and block b of Ainv left untouched where there is no inverse.  A is not written.  An Ainv of another shape, or one whose address
+ * range meets A's, returns -1. */
+int gf2_inverse_batch_dev(gf2_dmat *Ainv, gf2_dmat const *A, int n, int *singular, void *stream);
+/* which kernel a batch of this shape runs on, without a device: returns a variant id (>= 0), -1 if the shape is outside
+ * the limits (inverse != 0: also when ncols != m); out[0] = threads per workgroup, out[1] = matrices per workgroup, out[2] = LDS
+ * bytes per workgroup, out[3] = words per row held (identity included for inverse != 0).  Diagnostic, like gf2_tile_plan. */
+int gf2_elim_batch_plan(int m, int ncols, int inverse, long long out[4]);
 /* mzd_solve_left's contract on device matrices: A is m x n, B has >= max(m, n) rows and holds the right-hand
  * side in its first m rows; on return A holds its reduced row echelon form, rows 0 .. n-1 of B hold X (free variables 0) and every
  * further row of B is zero; *inconsistent = 1 when check != 0 and the system has no solution (B is then as mzd_solve_left leaves it).

@@ -142,6 +142,9 @@ _PROTOS = {
     "gf2_solve_left_dev": (_I, [DMatP, DMatP, _I, ctypes.POINTER(_I), ctypes.c_void_p]),
     "gf2_echelonize_dev": (_I, [DMatP, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.c_void_p]),
     "gf2_inverse_dev": (_I, [DMatP, DMatP, ctypes.POINTER(_I), ctypes.c_void_p]),
+    "gf2_echelonize_batch_dev": (_I, [DMatP, _I, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_inverse_batch_dev": (_I, [DMatP, DMatP, _I, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_elim_batch_plan": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
     "gf2_ple_dev": (_I, [DMatP, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.c_void_p]),
     "gf2_apply_p_dev": (_I, [DMatP, ctypes.POINTER(_I), _I, _I, _I, ctypes.c_void_p]),
     "gf2_pluq_solve_left_dev": (_I, [DMatP, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), DMatP, _I, ctypes.POINTER(_I),

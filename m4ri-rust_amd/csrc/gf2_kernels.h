@@ -71,6 +71,24 @@ hipError_t gf2k_elim_end_block(uint64_t *A, long long lda, long long aw, long lo
 // whole-matrix-in-LDS elimination for small matrices; hipErrorInvalidValue if the matrix does not qualify
 hipError_t gf2k_elim_small(uint64_t *A, long long lda, int m, int ncols, int limit, int full, int *rank_out, int *pivcols,
                            hipStream_t s);
+// batched elimination of small matrices (gf2_elim_batch.hip): `batch` matrices of m rows one below the other in S, the results in D
+// (echelon form: D == S; inverse != 0: D is the stack of inverses, ncols == m, singular[b] set).  ranks / pivcols / singular: device
+// arrays, may be null.  The kernel is gf2_elim_batch_plan's variant (the ids below); hipErrorInvalidValue outside its limits.
+enum {
+  GF2K_ELIM_BATCH_WAVE1 = 0,  // one wave per matrix, rows of 1 / 2 / 4 / 8 / 16 words in registers
+  GF2K_ELIM_BATCH_WAVE2 = 1,
+  GF2K_ELIM_BATCH_WAVE4 = 2,
+  GF2K_ELIM_BATCH_WAVE8 = 3,
+  GF2K_ELIM_BATCH_WAVE16 = 4,
+  GF2K_ELIM_BATCH_WAVE_INV = 5,  // n <= 64: one word of A, one of the identity
+  GF2K_ELIM_BATCH_LDS = 6,       // one workgroup per matrix, rows in LDS
+  GF2K_ELIM_BATCH_LDS_INV = 7,
+  GF2K_ELIM_BATCH_VARIANTS = 8
+};
+// threads of a wave-kernel workgroup (four waves = four matrices): the plan's block size and the kernel's matrix index both use it
+enum { GF2K_ELIM_BATCH_WAVE_THREADS = 256 };
+hipError_t gf2k_elim_batch(const uint64_t *S, long long lds_, uint64_t *D, long long ldd, int m, int ncols, int limit, int full,
+                           int inverse, long long batch, int *ranks, int *pivcols, int *singular, hipStream_t s);
 hipError_t gf2k_set_diag(uint64_t *M, long long ld, int n, long long col0, hipStream_t s);
 hipError_t gf2k_scatter_rows(uint64_t *X, long long ldx, const uint64_t *R, long long ldr, int words, const int *pivcols,
                              int rank, hipStream_t s);

@@ -231,6 +231,73 @@ def inverse(A, stream=None):
     return None if singular.value else out
 
 
+class _IntScratch:
+    """`count` device ints for a call that was given no array of its own: a dense DMat of 128 ints per row."""
+
+    def __init__(self, count):
+        self.count = count
+        self.mat = DMat((count + 127) // 128, 4096)
+
+    @property
+    def ptr(self):
+        return self.mat.s.data
+
+    def read(self, stream):
+        """the ints as a numpy array; waits for `stream`"""
+        self.mat._streams.add(stream)
+        return np.ascontiguousarray(self.mat.to_words(stream)).reshape(-1).view(np.int32)[:self.count].copy()
+
+
+def elim_batch_plan(m, ncols, inverse=False):
+    """Which kernel a batch of m x ncols matrices runs on (no device needed) -> (variant id, threads per workgroup, matrices per
+    workgroup, LDS bytes per workgroup, words per row held), or None when the shape is outside the limits."""
+    out = (ctypes.c_longlong * 4)()
+    v = _lib.lib().gf2_elim_batch_plan(m, ncols, int(bool(inverse)), out)
+    return None if v < 0 else (v, out[0], out[1], out[2], out[3])
+
+
+SKIP = 0  # for an output array of echelonize_batch / inverse_batch: do not compute it (the C call gets NULL)
+
+
+def echelonize_batch(A, m, full=True, ncols_limit=0, ranks=None, pivots=None, stream=None):
+    """Every m-row matrix of the stack A (matrix b = rows [b*m, (b+1)*m)) is replaced by its echelon form, each as echelonize() would
+    leave it.  -> (ranks, pivots).  Each of `ranks` (batch int32) and `pivots` (batch * P int32, P = min(m, limit), padded with -1) is
+      * a raw device address, e.g. a torch int32 tensor's data_ptr(): the kernel writes there, None is returned in its place;
+      * SKIP (0): the array is not wanted, None is returned in its place;
+      * None (the default): the wrapper allocates scratch, WAITS for `stream` and returns a numpy array (pivots: shape (batch, P)).
+    The call only enqueues on `stream` and returns -- asynchronous -- when neither argument is None."""
+    batch = A.nrows // m if m > 0 else 0
+    limit = ncols_limit if 0 < ncols_limit < A.ncols else A.ncols
+    P = max(min(m, limit), 0)
+    own_r = _IntScratch(batch) if ranks is None and batch > 0 else None
+    own_p = _IntScratch(batch * P) if pivots is None and batch * P > 0 else None
+    _lib.check(_lib.lib().gf2_echelonize_batch_dev(A._on(stream), m, int(bool(full)), int(ncols_limit),
+                                                   own_r.ptr if own_r else ranks, own_p.ptr if own_p else pivots, stream),
+               "gf2_echelonize_batch_dev")
+    out_r = out_p = None
+    if ranks is None:
+        out_r = own_r.read(stream) if own_r else np.zeros(0, dtype=np.int32)
+    if pivots is None:
+        out_p = (own_p.read(stream) if own_p else np.zeros(0, dtype=np.int32)).reshape(batch, P)
+    return out_r, out_p
+
+
+def inverse_batch(A, n, Ainv=None, singular=None, stream=None):
+    """Block b of Ainv = (block b of A)^-1 for the n x n blocks of the stack A; blocks without an inverse are flagged in `singular`
+    and left as they were in Ainv (a fresh Ainv: undefined).  -> (Ainv, singular).  `singular` (batch int32) is a raw device address or
+    SKIP (0) -- the call then only enqueues on `stream`, None is returned in its place -- or None: the wrapper allocates scratch, WAITS
+    for `stream` and returns a numpy array."""
+    if Ainv is None:
+        Ainv = DMat(A.nrows, A.ncols)
+    batch = A.nrows // n if n > 0 else 0
+    own = _IntScratch(batch) if singular is None and batch > 0 else None
+    _lib.check(_lib.lib().gf2_inverse_batch_dev(Ainv._on(stream), A._on(stream), n, own.ptr if own else singular, stream),
+               "gf2_inverse_batch_dev")
+    if singular is not None:
+        return Ainv, None
+    return Ainv, own.read(stream) if own else np.zeros(0, dtype=np.int32)
+
+
 def nullspace(A, stream=None):
     """A is reduced in place to its reduced row echelon form -> (K or None, rank, pivot columns): K is n x (n - rank) with A K = 0,
     its rows at the free columns the identity (ascending free columns); None when the rank is n.  Synchronous on `stream`."""
