@@ -1,13 +1,17 @@
-// api_internal.h -- shared between mzd_host.cpp and m4ri_hip_api.cpp
+// api_internal.h -- the runtime every translation unit of the library shares (runtime_host.cpp unless noted): error state, pooled
+// device memory, per-stream scratch, streams, and the host <-> device copies.  The launch planner has its own header (mul_plan.h).
 #pragma once
 [[noreturn]] void gf2_die(const char *msg);
 #include "../../include/m4ri_hip.h"
 #include <hip/hip_runtime.h>
+#include <memory>
+#include <mutex>
+#include <vector>
 mzd_t *gf2_mzd_init_uncleared(rci_t r, rci_t c);  // mzd_init without the memset (callers overwrite every word)
 // GPU-backed transpose of a host matrix (upload, 64x64-block kernel, download); 0 on success.  Used by mzd_transpose
 // for large matrices; the caller falls back to the host routine if it fails (this is not the multiply path).
 int gf2_host_transpose_gpu(mzd_t *dst, mzd_t const *src);
-int gf2_device_count(void);
+extern "C" int gf2_device_count(void);
 // drop the device copy kept for M by gf2_mzd_cache_on_device, if any (mzd_free and every in-place writer call this)
 void gf2_cache_forget(mzd_t const *M);
 // size dispatch of the drop-in entry points (gf2_small_host.cpp): M4RI_HIP_HOST_SMALL_WORK word operations, 0 = never
@@ -20,21 +24,105 @@ void gf2_pinned_free(void *p, size_t bytes);
 // destination (allocated when DST is NULL), or nullptr when A has no side copy
 mzd_t *gf2_transpose_from_side_copy(mzd_t *DST, mzd_t const *A);
 bool gf2_mzd_block_is_pinned(mzd_t const *M);
-// error reporting of the other translation units (gf2_ple.hip): set gf2_last_error and return the error code
+// error reporting: set gf2_last_error and return the error code
 int gf2_fail_msg(const char *what);
 int gf2_fail_hip(hipError_t e, const char *what);
-// scratch from the per-stream arena of m4ri_hip_api.cpp (grown on demand, reused by later calls on the stream, released by
-// gf2_trim); slots 0-3 belong to the products, 4 / 5 to gf2_trsm.hip (block inverses / a leaf's result)
-int gf2_stream_scratch(hipStream_t s, size_t bytes, void **out, int slot);
+#define HIP_TRY(expr)                                       \
+  do {                                                      \
+    hipError_t _e = (expr);                                 \
+    if (_e != hipSuccess) return gf2_fail_hip(_e, #expr);   \
+  } while (0)
+#define GF2_RC(expr)     \
+  do {                   \
+    int _rc = (expr);    \
+    if (_rc) return _rc; \
+  } while (0)
+int gf2_require_device();  // 0, or the "no usable HIP device" error
+// scratch from the per-stream arena (grown on demand, reused by later calls on the stream, released by gf2_trim).  Slot 0: Strassen
+// operand arena / transposed operand of the naive entry; 1: split-K and stream-K partial tiles; 2: packed A; 3: the copies of a padded
+// product; 4 / 5: gf2_trsm.hip (block inverses / a leaf's result)
+int gf2_stream_scratch(hipStream_t s, size_t bytes, void **out, int slot = 0);
 // counts a run of a host routine of the size dispatch (gf2_host_small_calls)
 void gf2_note_host_small_call();
-// pooled device memory of m4ri_hip_api.cpp for the other translation units (gf2_nullspace.hip).  gf2_dev_free is not stream-ordered: the
-// caller has synchronised every stream that touched the block
+// pooled device memory.  gf2_dev_free is NOT stream-ordered: the caller guarantees that no queued work still touches the block (it
+// synchronised its stream, or it goes through gf2_dmat_free / gf2_dmat_free_async)
 int gf2_dev_alloc(void **p, size_t bytes);
 void gf2_dev_free(void *p, size_t bytes);
+// what an arena on stream s may grow to: 95 % of what the driver reports free plus what the library holds for it already (the block
+// cache and the stream's slot 0 are handed back before a larger arena is allocated); SIZE_MAX when the driver does not say
+size_t gf2_dev_arena_limit(hipStream_t s);
+struct DevBuf {  // a pooled block for the length of a scope
+  void *p = nullptr;
+  size_t bytes = 0;
+  int alloc(size_t b) {
+    bytes = b ? b : 8;
+    return gf2_dev_alloc(&p, bytes);
+  }
+  ~DevBuf() { gf2_dev_free(p, bytes); }
+  template <class T>
+  T *as() const { return static_cast<T *>(p); }
+};
+int gf2_private_stream(hipStream_t *out);  // the calling thread's own stream on the current device (host entry points)
+// Side streams + events for one main stream (copy streams of the host pipelines); cached per (device, stream), never destroyed
+struct SideStream {
+  hipStream_t s2 = nullptr;
+  hipStream_t s3 = nullptr;  // second copy stream of the host pipeline (downloads; s2 carries the uploads)
+  std::vector<hipEvent_t> ev;
+};
+int gf2_side_stream(hipStream_t s, int nevents, SideStream **out, bool want_s3 = false);
+// Products that use the per-stream workspace enqueue several kernels that must stay contiguous on the stream
+// (another host thread enqueueing on the SAME stream in between would reuse the arena under them).
+extern std::mutex gf2_enqueue_mu;
+// bench.py's roofline: HIP events on the launch stream around the tile-kernel launches of one (batched) product
+struct ProfScope {
+  hipEvent_t a{}, b{};
+  bool on = false;
+  hipStream_t s;
+  explicit ProfScope(hipStream_t s_);
+  ~ProfScope();
+};
+bool gf2_prof_is_on();  // gf2_prof_enable's switch (gf2_nullspace.hip times its assembly launch while it is on)
+
+// device matrices <-> host mzd_t
+static inline long long dev_ld_for(int ncols) {
+  const long long w = ((long long)ncols + 63) >> 6;
+  return w <= 1 ? (w ? w : 1) : ((w + 1) & ~1ll);
+}
+void gf2_dmat_release(gf2_dmat *M);  // gf2_dmat_free without the wait: the caller has waited for every stream that touched M
+// rows [r0, r0 + dst->nrows) of src -> dst; asynchronous: `src` must stay untouched until the stream has passed the copy
+int gf2_upload_rows_async(gf2_dmat *dst, mzd_t const *src, int r0, hipStream_t s);
+// src -> rows [r0, r0 + src->nrows) of a host matrix; returns when they are complete in host memory
+int gf2_download_rows(mzd_t *dst, int r0, gf2_dmat const *src, hipStream_t s);
+
+// the products on device matrices (mul_dev_host.cpp); gf2_mul_dispatch takes gf2_enqueue_mu unless sync_free (a private stream)
+int gf2_mul_m4rm_plain(gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B, int accumulate, hipStream_t s);
+int gf2_mul_dispatch(gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B, int accumulate, int algo, int param, hipStream_t s, bool sync_free);
+
+// host operands on the device (m4ri_hip_api.cpp)
+struct CachedOperand;
+struct DMatOwner {
+  gf2_dmat d{};
+  std::shared_ptr<CachedOperand> borrowed;  // d belongs to the operand cache, kept alive by this reference
+  bool released = false;                    // ownership moved elsewhere
+  ~DMatOwner() {
+    if (!borrowed && !released) gf2_dmat_release(&d);  // every user synchronises its stream before the owner goes out of scope
+  }
+};
+std::shared_ptr<CachedOperand> gf2_cache_lookup(const mzd_t *M);
+// device copy of rows [r0, r1) of M (of all of M) whose row stride equals the host row stride when the host block is contiguous
+int gf2_to_device_rows(DMatOwner &o, const mzd_t *M, int r0, int r1, hipStream_t s, bool copy);
+int gf2_to_device(DMatOwner &o, const mzd_t *M, hipStream_t s, bool copy);
+// M4RI_HIP_DEVICES = one ordinal: every host entry point runs on that device.  RAII: sets it, restores the caller's.
+struct PinnedDevice {
+  int prev = -1;
+  bool switched = false;
+  PinnedDevice();
+  ~PinnedDevice();
+  PinnedDevice(const PinnedDevice &) = delete;
+  PinnedDevice &operator=(const PinnedDevice &) = delete;
+};
+
 // the reduced row echelon form of gf2_echelonize_dev(full = 1, all columns) that also hands over the elimination's device array of pivot
 // columns: *pivcols_dev (null when the matrix is empty) is released with gf2_dev_free(*pivcols_dev, *pivcols_bytes); pivcols_host may
-// be null.  Synchronous on s.
+// be null.  Synchronous on s.  (elim_host.cpp)
 int gf2_rref_keep_pivots_dev(gf2_dmat *A, int *rank, int *pivcols_host, void **pivcols_dev, size_t *pivcols_bytes, hipStream_t s);
-// gf2_prof_enable's switch (gf2_nullspace.hip times its assembly launch while it is on)
-bool gf2_prof_is_on();

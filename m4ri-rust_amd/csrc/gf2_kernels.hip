@@ -42,6 +42,7 @@
 #include <type_traits>
 #include <utility>
 #include "gf2_kernels.h"
+#include "gf2_variants.h"
 
 typedef uint64_t u64;
 typedef uint32_t u32;
@@ -2389,7 +2390,7 @@ __global__ __launch_bounds__(256) void gf2_xor2d_kernel(u64 *__restrict__ C, lon
 }
 
 // dst (drows x dwords words, dense) = src (srows x swords) in its top left corner, zeros elsewhere: operands padded up to
-// dimensions that divide by the Strassen level plan (m4ri_hip_api.cpp, mul_strassen_padded)
+// dimensions that divide by the Strassen level plan (mul_dev_host.cpp, mul_strassen_padded)
 // dst (drows x dwords, zero padded) <- src (srows x scols bits); 16-byte accesses where both rows allow them (ldd, lds_ even and
 // 16-byte aligned bases: `vec`), one block row per blockIdx.y step (no division in the loop)
 // The source's last word is masked to its `scols` columns: a window whose column end is not a multiple of 64 shares that word with
@@ -2766,10 +2767,7 @@ struct gf2k_split3_srcs {
   const u64 *b[7];  // second quadrant of the virtual level's combination, or nullptr
 };
 
-// quadrants (0 = X11, 1 = X12, 2 = X21, 3 = X22) that combination q of a side adds up; second entry -1: a plain copy
-__device__ constexpr int kStrassenSupp[2][7][2] = {
-    {{0, 3}, {2, 3}, {0, -1}, {3, -1}, {0, 1}, {2, 0}, {1, 3}},   // A side: A11+A22, A21+A22, A11, A22, A11+A12, A21+A11, A12+A22
-    {{0, 3}, {0, -1}, {1, 3}, {2, 0}, {3, -1}, {0, 1}, {2, 3}}};  // B side: B11+B22, B11, B12+B22, B21+B11, B22, B11+B12, B21+B22
+__device__ constexpr int kStrassenSupp[2][7][2] = GF2_STRASSEN_SUPP;  // (gf2_variants.h: the host walks the same table)
 
 template <int SIDE, bool PACK, bool NT = false>
 __global__ __launch_bounds__(256) void gf2_strassen_split3_kernel(u64 *__restrict__ dst, long long ldd, long long dstStride,
@@ -2958,7 +2956,7 @@ __global__ __launch_bounds__(256) void gf2_packB_kernel(u32 *__restrict__ Bp, lo
 #endif  // GF2K_DEV_VARIANTS
 
 // ---------------------------------------------------------------------------------------------
-// launchers (internal C ABI used by m4ri_hip_api.cpp)
+// launchers (internal C ABI used by mul_dev_host.cpp and the other host units)
 // ---------------------------------------------------------------------------------------------
 
 static inline int grid_for(long long total, int block = 256, int cap = 256 * 8) {
@@ -2968,35 +2966,12 @@ static inline int grid_for(long long total, int block = 256, int cap = 256 * 8) 
   return (int)g;
 }
 
-// variants: 9 / 10 / 11 / 12 = v8 with 4096 / 2048 / 1024 / 512-row tiles (512 columns); 21 / 22 / 23 = v9 with 4096 / 2048 / 1024-row
-// tiles of 128 columns; 8x = v6; 90-99 = the legacy v7 (development builds)
-static int cfg_v8_rg(int cfg) {
-#ifdef GF2K_DEV_VARIANTS
-  if (cfg >= 13 && cfg <= 16) return 8 >> (cfg - 13);  // read window of three steps (kbench A/B)
-  if (cfg >= 17 && cfg <= 19) return 8 >> (cfg - 17);  // read window of one step
-#endif
-  return cfg == 9 ? 8 : cfg == 10 ? 4 : cfg == 11 ? 2 : cfg == 12 ? 1 : 0;
-}
-static int cfg_v9_rg(int cfg) {  // the tall-narrow experiment (tools/gf2_kernels_v9_experiment.inc): development builds only
-#ifdef GF2K_DEV_VARIANTS
-  return cfg == 21 ? 8 : cfg == 22 ? 4 : cfg == 23 ? 2 : 0;
-#else
-  (void)cfg;
-  return 0;
-#endif
-}
-static bool cfg_is_v7(int cfg) { return cfg_v8_rg(cfg) > 0 || (cfg >= 90 && cfg < 100); }
-static bool cfg_is_v56(int cfg) { return cfg == 8 || (cfg >= 80 && cfg < 90); }
-extern "C" int gf2k_m4rm_rows_per_tile(int cfg) {
-  if (cfg_v8_rg(cfg)) return 512 * cfg_v8_rg(cfg);
-  if (cfg_v9_rg(cfg)) return 512 * cfg_v9_rg(cfg);
-  return (cfg == 1 || cfg == 20) ? 256 : cfg_is_v7(cfg) ? 4096 : cfg_is_v56(cfg) ? 2048 : 1024;
-}
-extern "C" int gf2k_m4rm_cols_per_tile(int cfg) { return cfg_v9_rg(cfg) ? 128 : cfg_is_v7(cfg) ? 512 : cfg_is_v56(cfg) ? 1024 : 2048; }
-extern "C" long long gf2k_m4rm_streamk_words(int cfg, int nseg) {
-  if (cfg_v9_rg(cfg)) return 2ll * nseg * 512 * cfg_v9_rg(cfg) * 2;
-  return cfg_v8_rg(cfg) ? 2ll * nseg * 512 * cfg_v8_rg(cfg) * 8 : 0;
-}
+// the variant table (rows and columns per tile, families, who reads packed A) is gf2_variants.h's: the planner reads the same one
+static int cfg_v8_rg(int cfg) { return gf2_variant_of(cfg).v8_rg; }
+static int cfg_v9_rg(int cfg) { return gf2_variant_of(cfg).v9_rg; }
+extern "C" int gf2k_m4rm_rows_per_tile(int cfg) { return gf2_variant_of(cfg).rows; }
+extern "C" int gf2k_m4rm_cols_per_tile(int cfg) { return gf2_variant_of(cfg).cols; }
+extern "C" long long gf2k_m4rm_streamk_words(int cfg, int nseg) { return gf2_streamk_words(gf2_variant_of(cfg), nseg); }
 
 // The dynamic-LDS limit of a kernel is per device; hipFuncSetAttribute costs host time that short kernels launched back
 // to back notice, so it is issued once per (kernel, device).
@@ -3044,20 +3019,11 @@ static hipError_t launch_v8(gf2k_mul_args a, int cfg, int RG, hipStream_t stream
   a.kwords = v8_flags;
 #endif
   long long n_rem = a.P && Q > 0 ? std::min<long long>(std::max(a.n_rem, 0), T) : 0;
-  int nseg = 0, seg = 0;
-  if (n_rem > 0) {
-    const long long gtot = n_rem * Q, want = a.nseg > 0 ? a.nseg : 256;
-    long long sg = (gtot + want - 1) / want;
-    if (sg > Q) sg = Q;  // a segment spans at most two tiles
-    if (sg < 1) sg = 1;
-    const long long ns = (gtot + sg - 1) / sg;
-    if (ns > 0x7fffff00LL - T || gf2k_m4rm_streamk_words(cfg, (int)ns) > a.p_words || (ns <= n_rem && sg == Q)) {
-      n_rem = 0;  // no room for the partial tiles (or nothing would be split): whole tiles
-    } else {
-      nseg = (int)ns;
-      seg = (int)sg;
-    }
-  }
+  // the planner's cut (gf2_variants.h), refused here when the partial tiles have no room or the workgroups do not fit a grid: whole tiles
+  gf2_streamk_cut cut = gf2_streamk_cut_of(T, Q, n_rem, a.nseg);
+  if (cut.nseg > 0x7fffff00LL - T || gf2_streamk_words(gf2_variant_of(cfg), cut.nseg) > a.p_words) cut = {0, 0, 0};
+  n_rem = cut.n_rem;
+  const int nseg = (int)cut.nseg, seg = (int)cut.seg;
   a.n_rem = (int)n_rem;
   a.nseg = nseg;
   a.seg_slabs = seg;
@@ -3121,7 +3087,7 @@ static hipError_t launch_v8(gf2k_mul_args a, int cfg, int RG, hipStream_t stream
 // with -DGF2K_DEV_VARIANTS (tools/libm4ri_hip_dev.so for tools/kbench) and is hipErrorInvalidValue in libm4ri_hip.so.
 extern "C" hipError_t gf2k_m4rm(gf2k_mul_args a, int cfg, hipStream_t stream) {
   if (a.m <= 0 || a.n <= 0 || a.batch <= 0) return hipSuccess;
-  if (a.a_packed && cfg != 8 && !cfg_is_v7(cfg) && !cfg_v9_rg(cfg)) return hipErrorInvalidValue;  // only v6 / v7 / v8 / v9 read the packed layout
+  if (a.a_packed && !gf2_variant_of(cfg).reads_packed) return hipErrorInvalidValue;  // only v6 / v7 / v8 / v9 read the packed layout
   if (const int RG = cfg_v8_rg(cfg)) return launch_v8(a, cfg, RG, stream);
   if (const int RG = cfg_v9_rg(cfg)) return launch_v8(a, cfg, RG, stream);
   const int R = gf2k_m4rm_rows_per_tile(cfg);
@@ -3507,7 +3473,7 @@ static hipError_t tallskinny_impl(const u64 *A, long long lda, const u64 *B, lon
   if (nw == 1) {  // generation kernel (replicated tables, skew inside a 64-bit word)
 #ifndef GF2K_DEV_VARIANTS
     // Every shape that used to come here (n <= 64, 256 < l <= 1024, at least 2^19 rows) is taken by the slab table kernel first
-    // (ts_long_shape, m4ri_hip_api.cpp), so the shipped library does not carry an instantiation no call can reach
+    // (ts_long_shape, mul_plan_host.cpp), so the shipped library does not carry an instantiation no call can reach
     // (tools/kernel_coverage.py, retirement rule of DESIGN 4.1); development builds keep it for A/B runs (M4RI_HIP_TS7=0).
     return hipErrorInvalidValue;
 #else
@@ -3899,7 +3865,7 @@ extern "C" hipError_t gf2k_strassen_merge3(u64 *dst, long long ldd, long long ds
   const long long total = (long long)h * w;
   const int gx = grid_for(total, 256, (8192 + batch * groups - 1) / (batch * groups));
   // non-temporal loads: -7 % (1.25 -> 1.15 ms); and stores: 1.11-1.16 -> 1.06-1.09 ms at 65536^3
-  static const int ntl = GF2K_DEV_ENV("M4RI_HIP_PASS_NTL", 1);
+  static const int ntl = GF2K_DEV_ENV("M4RI_HIP_PASS_NTL", 1);  // the products are read once: non-temporal loads, -7 % (1.25 -> 1.15 ms)
 #ifdef GF2K_DEV_VARIANTS
   if (!ntl)
     hipLaunchKernelGGL(gf2_strassen_merge3_kernel<false>, dim3(gx, groups, batch), dim3(256), 0, stream, dst, ldd, dstStride, src, lds_,

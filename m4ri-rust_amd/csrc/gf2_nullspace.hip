@@ -120,22 +120,6 @@ __global__ void __launch_bounds__(256) nullspace_assemble(const u64 *__restrict_
 
 inline int words_of(long long bits) { return (int)((bits + 63) >> 6); }
 
-#define NS_TRY(expr)                                      \
-  do {                                                    \
-    hipError_t _e = (expr);                               \
-    if (_e != hipSuccess) return gf2_fail_hip(_e, #expr); \
-  } while (0)
-
-struct DevBlock {
-  void *p = nullptr;
-  size_t bytes = 0;
-  int alloc(size_t b) {
-    bytes = b ? b : 8;
-    return gf2_dev_alloc(&p, bytes);
-  }
-  ~DevBlock() { gf2_dev_free(p, bytes); }  // every exit has synchronised the stream
-};
-
 // gf2_prof_enable is on: events around the assembly launch; the last call's time on this thread
 thread_local double tls_assemble_ms = 0;
 struct EventPair {
@@ -159,7 +143,7 @@ extern "C" int gf2_nullspace_dev(gf2_dmat *A, gf2_dmat *K, int *rank, int *pivot
   *rank = 0;
   *K = gf2_dmat{nullptr, 0, n, 0};
   if (n == 0) return 0;
-  DevBlock piv;  // the elimination's own buffer of pivot columns, handed over
+  DevBuf piv;  // the elimination's own buffer of pivot columns, handed over
   if (int rc = gf2_rref_keep_pivots_dev(A, rank, pivot_cols, &piv.p, &piv.bytes, s)) {
     (void)hipStreamSynchronize(s);
     return rc;
@@ -170,7 +154,7 @@ extern "C" int gf2_nullspace_dev(gf2_dmat *A, gf2_dmat *K, int *rank, int *pivot
   const int kw = words_of(d);
   // one block: the masks, the control words, the start entries, the row kinds
   const size_t mask_bytes = (size_t)nw * sizeof(u64), ctl_bytes = (size_t)nw * CTL_WORDS * sizeof(u64), start_bytes = (size_t)kw * sizeof(int2);
-  DevBlock prep;
+  DevBuf prep;
   if (int rc = prep.alloc(mask_bytes + ctl_bytes + start_bytes + (size_t)n * sizeof(int))) return rc;
   u64 *fmask = static_cast<u64 *>(prep.p), *ctl = fmask + nw;
   int2 *start = reinterpret_cast<int2 *>(static_cast<char *>(prep.p) + mask_bytes + ctl_bytes);
@@ -187,22 +171,22 @@ extern "C" int gf2_nullspace_dev(gf2_dmat *A, gf2_dmat *K, int *rank, int *pivot
     if (grid.y > 65535u) return gf2_fail_msg("gf2_nullspace_dev: the basis is too wide for one launch");
     hipLaunchKernelGGL(nullspace_prepare, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, pivcols, r, n, nw, kw, fmask, ctl, rowinfo,
                        start);
-    NS_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     const bool prof = gf2_prof_is_on();
     EventPair ev;
     if (prof) {
-      NS_TRY(hipEventCreate(&ev.a));
-      NS_TRY(hipEventCreate(&ev.b));
-      NS_TRY(hipEventRecord(ev.a, s));
+      HIP_TRY(hipEventCreate(&ev.a));
+      HIP_TRY(hipEventCreate(&ev.b));
+      HIP_TRY(hipEventRecord(ev.a, s));
     }
     hipLaunchKernelGGL(nullspace_assemble, grid, dim3(wx, ry), 0, s, static_cast<const u64 *>(A->data), (long long)A->ld, nw, fmask, ctl,
                        rowinfo, start, static_cast<u64 *>(K->data), (long long)K->ld, n, kw, d);
-    NS_TRY(hipGetLastError());
-    if (prof) NS_TRY(hipEventRecord(ev.b, s));
-    NS_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    if (prof) HIP_TRY(hipEventRecord(ev.b, s));
+    HIP_TRY(hipStreamSynchronize(s));
     if (prof) {
       float ms = 0;
-      NS_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+      HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
       tls_assemble_ms = ms;
     }
     return 0;

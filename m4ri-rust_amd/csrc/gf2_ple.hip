@@ -247,16 +247,6 @@ inline u64 last_mask(long long bits) { return (bits & 63) ? ((1ull << (bits & 63
 inline long long even_ld(long long w) { return (w + 1) & ~1ll; }  // device matrices keep even row strides
 inline unsigned grid_of(long long n, int b) { return (unsigned)((n + b - 1) / b); }
 
-#define PLE_TRY(expr)                                                                \
-  do {                                                                               \
-    hipError_t _e = (expr);                                                          \
-    if (_e != hipSuccess) return gf2_fail_hip(_e, #expr);                            \
-  } while (0)
-#define PLE_RC(expr)            \
-  do {                          \
-    int _rc = (expr);           \
-    if (_rc) return _rc;        \
-  } while (0)
 
 struct DBuf {
   void *p = nullptr;
@@ -283,10 +273,10 @@ inline gf2_dmat win(const gf2_dmat &A, long long r, long long c, int rows, int c
 // dst rows [0, rows) x words = src rows perm[i] (perm null: identity) through scratch when they alias; lastmask on the last word
 int gather_rows(const gf2_dmat &D, const int *perm_dev, int rows, int words, u64 lastmask, u64 *scratch, hipStream_t s) {
   if (rows <= 0 || words <= 0) return 0;
-  PLE_TRY(hipMemcpy2DAsync(scratch, (size_t)words * 8, D.data, (size_t)D.ld * 8, (size_t)words * 8, rows, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpy2DAsync(scratch, (size_t)words * 8, D.data, (size_t)D.ld * 8, (size_t)words * 8, rows, hipMemcpyDeviceToDevice, s));
   hipLaunchKernelGGL(ple_gather, dim3(grid_of((long long)rows * words, 256)), dim3(256), 0, s, static_cast<u64 *>(D.data), D.ld,
                      scratch, (long long)words, perm_dev, rows, words, lastmask);
-  PLE_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
@@ -310,14 +300,14 @@ int panel(PleCtx &c, int r0, int c0, int c1, int *rank) {
   const u64 vmask = last_mask(c1 - c0);
   u64 *A0 = static_cast<u64 *>(c.A.data) + (long long)r0 * c.A.ld + (c0 >> 6);
   u64 *col = c.scratch;
-  PLE_TRY(hipMemcpy2DAsync(col, 8, A0, (size_t)c.A.ld * 8, 8, cnt, hipMemcpyDeviceToDevice, c.s));
+  HIP_TRY(hipMemcpy2DAsync(col, 8, A0, (size_t)c.A.ld * 8, 8, cnt, hipMemcpyDeviceToDevice, c.s));
   const int nchunk = (cnt + PANEL_CHUNK - 1) / PANEL_CHUNK;
   hipLaunchKernelGGL(ple_panel_scan, dim3(nchunk), dim3(64), 0, c.s, col, cnt, vmask, c.cand);
   hipLaunchKernelGGL(ple_panel_pivots, dim3(1), dim3(64), 0, c.s, col, nchunk, vmask, c.cand, c.tab, c.qcol + r0, c0);
   hipLaunchKernelGGL(ple_panel_apply, dim3(grid_of(cnt, 256)), dim3(256), 0, c.s, col, cnt, vmask, c.tab, A0, c.A.ld, c.pi + r0);
-  PLE_TRY(hipGetLastError());
-  PLE_TRY(hipMemcpyAsync(c.rank_host, c.tab + 256, 8, hipMemcpyDeviceToHost, c.s));
-  PLE_TRY(hipStreamSynchronize(c.s));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(c.rank_host, c.tab + 256, 8, hipMemcpyDeviceToHost, c.s));
+  HIP_TRY(hipStreamSynchronize(c.s));
   *rank = (int)*c.rank_host;
   return 0;
 }
@@ -329,29 +319,29 @@ int ple_rec(PleCtx &c, int r0, int c0, int c1, int depth, int *rank) {
   const int cmid = c0 + 64 * ((words_of(c1 - c0) + 1) / 2);
   const int cnt = c.m - r0;
   int r1 = 0, r2 = 0;
-  PLE_RC(ple_rec(c, r0, c0, cmid, depth + 1, &r1));
+  GF2_RC(ple_rec(c, r0, c0, cmid, depth + 1, &r1));
   int *st = c.stash[depth];
-  PLE_TRY(hipMemcpyAsync(st + r0, c.pi + r0, (size_t)cnt * sizeof(int), hipMemcpyDeviceToDevice, c.s));
+  HIP_TRY(hipMemcpyAsync(st + r0, c.pi + r0, (size_t)cnt * sizeof(int), hipMemcpyDeviceToDevice, c.s));
   // right half in the left half's row order
   gf2_dmat R = win(c.A, r0, cmid, cnt, c1 - cmid);
-  PLE_RC(gather_rows(R, st + r0, cnt, words_of(c1 - cmid), last_mask(c1 - cmid), c.scratch, c.s));
+  GF2_RC(gather_rows(R, st + r0, cnt, words_of(c1 - cmid), last_mask(c1 - cmid), c.scratch, c.s));
   if (r1 > 0) {
     gf2_dmat L11 = win(c.A, r0, c0, r1, r1), A12 = win(c.A, r0, cmid, r1, c1 - cmid);
-    PLE_RC(gf2_trsm_dev(&L11, &A12, 0, 0, c.s));  // E12 = L11^-1 A12
+    GF2_RC(gf2_trsm_dev(&L11, &A12, 0, 0, c.s));  // E12 = L11^-1 A12
     if (cnt > r1) {
       gf2_dmat C = win(c.A, r0 + r1, cmid, cnt - r1, c1 - cmid), L = win(c.A, r0 + r1, c0, cnt - r1, r1),
                E = win(c.A, r0, cmid, r1, c1 - cmid);
-      PLE_RC(gf2_mul_dev(&C, &L, &E, 1, 0, 0, c.s));  // A22 ^= L21 E12
+      GF2_RC(gf2_mul_dev(&C, &L, &E, 1, 0, 0, c.s));  // A22 ^= L21 E12
     }
   }
   if (cnt > r1) {
-    PLE_RC(ple_rec(c, r0 + r1, cmid, c1, depth + 1, &r2));
+    GF2_RC(ple_rec(c, r0 + r1, cmid, c1, depth + 1, &r2));
     const int rest = cnt - r1;
     // left half's rows below the left pivots in the right half's order (whole words: [c0, cmid) lies inside the matrix)
     gf2_dmat Lh = win(c.A, r0 + r1, c0, rest, cmid - c0);
-    PLE_RC(gather_rows(Lh, c.pi + r0 + r1, rest, words_of(cmid - c0), ~0ull, c.scratch, c.s));
+    GF2_RC(gather_rows(Lh, c.pi + r0 + r1, rest, words_of(cmid - c0), ~0ull, c.scratch, c.s));
     hipLaunchKernelGGL(ple_compose, dim3(grid_of(rest, 256)), dim3(256), 0, c.s, c.pi + r0 + r1, st + r0, r1, rest);
-    PLE_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (r2 > 0 && r1 < cmid - c0) {  // right L from column cmid to column c0 + r1
       const int sw = words_of(r2);
       u64 *row0 = static_cast<u64 *>(c.A.data) + (long long)(r0 + r1) * c.A.ld;
@@ -360,7 +350,7 @@ int ple_rec(PleCtx &c, int r0, int c0, int c1, int depth, int *rank) {
       const int wlo = (c0 + r1) >> 6, whi = words_of(cmid + r2);
       hipLaunchKernelGGL(ple_compress_place, dim3(grid_of((long long)rest * (whi - wlo), 256)), dim3(256), 0, c.s, row0, c.A.ld,
                          rest, cmid, c0 + r1, r2, c.scratch, sw, wlo, whi - wlo);
-      PLE_TRY(hipGetLastError());
+      HIP_TRY(hipGetLastError());
     }
   }
   *rank = r1 + r2;
@@ -384,11 +374,11 @@ int apply_rows(const gf2_dmat &A, const std::vector<int> &map, hipStream_t s) {
   const int rows = A.nrows, words = words_of(A.ncols);
   if (rows == 0 || words == 0) return 0;
   DBuf dm, sc;
-  PLE_RC(dm.alloc((size_t)rows * sizeof(int)));
-  PLE_RC(sc.alloc((size_t)rows * words * 8));
-  PLE_TRY(hipMemcpyAsync(dm.p, map.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice, s));
-  PLE_RC(gather_rows(A, dm.as<int>(), rows, words, last_mask(A.ncols), sc.as<u64>(), s));
-  PLE_TRY(hipStreamSynchronize(s));  // map and scratch are freed on return
+  GF2_RC(dm.alloc((size_t)rows * sizeof(int)));
+  GF2_RC(sc.alloc((size_t)rows * words * 8));
+  HIP_TRY(hipMemcpyAsync(dm.p, map.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice, s));
+  GF2_RC(gather_rows(A, dm.as<int>(), rows, words, last_mask(A.ncols), sc.as<u64>(), s));
+  HIP_TRY(hipStreamSynchronize(s));  // map and scratch are freed on return
   return 0;
 }
 
@@ -400,21 +390,21 @@ static int apply_cols_dev(const gf2_dmat &A, const std::vector<int> &map, hipStr
   if (m == 0 || n == 0) return 0;
   const long long tw = even_ld(words_of(m)), aw = even_ld(words_of(n));
   DBuf t1, t2, dm;
-  PLE_RC(t1.alloc((size_t)std::max<long long>((long long)n * tw, (long long)m * aw) * 8));
-  PLE_RC(t2.alloc((size_t)n * tw * 8));
-  PLE_RC(dm.alloc((size_t)n * sizeof(int)));
-  PLE_TRY(hipMemcpyAsync(dm.p, map.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+  GF2_RC(t1.alloc((size_t)std::max<long long>((long long)n * tw, (long long)m * aw) * 8));
+  GF2_RC(t2.alloc((size_t)n * tw * 8));
+  GF2_RC(dm.alloc((size_t)n * sizeof(int)));
+  HIP_TRY(hipMemcpyAsync(dm.p, map.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
   gf2_dmat Ac = A, T{t1.as<u64>(), tw, n, m};
-  PLE_RC(gf2_transpose_dev(&T, &Ac, s));  // T = A^T
+  GF2_RC(gf2_transpose_dev(&T, &Ac, s));  // T = A^T
   hipLaunchKernelGGL(ple_gather, dim3(grid_of((long long)n * tw, 256)), dim3(256), 0, s, t2.as<u64>(), tw, t1.as<u64>(), tw,
                      dm.as<int>(), n, (int)tw, ~0ull);
-  PLE_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   gf2_dmat G{t2.as<u64>(), tw, n, m}, U{t1.as<u64>(), aw, m, n};
-  PLE_RC(gf2_transpose_dev(&U, &G, s));  // U = (gathered A^T)^T
+  GF2_RC(gf2_transpose_dev(&U, &G, s));  // U = (gathered A^T)^T
   hipLaunchKernelGGL(ple_gather, dim3(grid_of((long long)m * words_of(n), 256)), dim3(256), 0, s, static_cast<u64 *>(A.data), A.ld,
                      t1.as<u64>(), aw, (const int *)nullptr, m, words_of(n), last_mask(n));
-  PLE_TRY(hipGetLastError());
-  PLE_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s));
   return 0;
 }
 
@@ -463,18 +453,18 @@ extern "C" int gf2_ple_dev(gf2_dmat *A, int pluq, int *P, int *Q, int *rank, voi
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int aw = words_of(n);
   DBuf pi, qc, sc, cand, tab;
-  PLE_RC(pi.alloc((size_t)m * sizeof(int)));
-  PLE_RC(qc.alloc((size_t)std::min(m, n) * sizeof(int)));
+  GF2_RC(pi.alloc((size_t)m * sizeof(int)));
+  GF2_RC(qc.alloc((size_t)std::min(m, n) * sizeof(int)));
   const long long swords = std::max<long long>((long long)m * ((aw + 1) / 2), (long long)m * (words_of(std::min(m, n)) + 1));
-  PLE_RC(sc.alloc((size_t)swords * 8));
-  PLE_RC(cand.alloc((size_t)((m + PANEL_CHUNK - 1) / PANEL_CHUNK) * 65 * sizeof(int)));
-  PLE_RC(tab.alloc(257 * 8));
+  GF2_RC(sc.alloc((size_t)swords * 8));
+  GF2_RC(cand.alloc((size_t)((m + PANEL_CHUNK - 1) / PANEL_CHUNK) * 65 * sizeof(int)));
+  GF2_RC(tab.alloc(257 * 8));
   u64 *rank_host = nullptr;
-  PLE_TRY(hipHostMalloc(reinterpret_cast<void **>(&rank_host), 8, 0));
+  HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&rank_host), 8, 0));
   int depth = 1;
   for (int w = aw; w > 1; w = (w + 1) / 2) ++depth;  // levels of the column recursion
   DBuf stash;
-  PLE_RC(stash.alloc((size_t)depth * m * sizeof(int)));
+  GF2_RC(stash.alloc((size_t)depth * m * sizeof(int)));
   PleCtx c{*A, m, n, s, pi.as<int>(), qc.as<int>(), {}, sc.as<u64>(), cand.as<int>(), tab.as<u64>(), rank_host};
   for (int d = 0; d < depth; ++d) c.stash.push_back(stash.as<int>() + (size_t)d * m);
   int r = 0;
@@ -498,16 +488,16 @@ extern "C" int gf2_ple_dev(gf2_dmat *A, int pluq, int *P, int *Q, int *rank, voi
     // the diagonal are zero, so the swaps that would touch L are no-ops and the whole rows can be permuted
     DBuf eb;
     const long long eld = even_ld(aw);
-    PLE_RC(eb.alloc((size_t)r * eld * 8));
+    GF2_RC(eb.alloc((size_t)r * eld * 8));
     gf2_dmat E{eb.as<u64>(), eld, r, n};
     hipLaunchKernelGGL(ple_tri, dim3(grid_of((long long)r * aw, 256)), dim3(256), 0, s, eb.as<u64>(), eld,
                        static_cast<const u64 *>(A->data), A->ld, r, aw, last_mask(n), 0);
-    PLE_TRY(hipGetLastError());
-    PLE_RC(apply_cols_dev(E, perm_map(Q, n, n, false), s));
+    HIP_TRY(hipGetLastError());
+    GF2_RC(apply_cols_dev(E, perm_map(Q, n, n, false), s));
     hipLaunchKernelGGL(ple_tri, dim3(grid_of((long long)r * aw, 256)), dim3(256), 0, s, static_cast<u64 *>(A->data), A->ld,
                        eb.as<const u64>(), eld, r, aw, last_mask(n), 1);
-    PLE_TRY(hipGetLastError());
-    PLE_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
   }
   return 0;
 }
@@ -530,27 +520,27 @@ extern "C" int gf2_pluq_solve_left_dev(gf2_dmat const *A, int rank, const int *P
   const int bw = words_of(kb);
   const u64 bmask = last_mask(kb);
   gf2_dmat Bm = win(*B, 0, 0, m, kb);
-  PLE_RC(apply_rows(Bm, perm_map(P, m, m, false), s));                  // P B
+  GF2_RC(apply_rows(Bm, perm_map(P, m, m, false), s));                  // P B
   gf2_dmat T11 = win(*A, 0, 0, rank, rank), Y = win(*B, 0, 0, rank, kb);  // L11 and U11 share the block: gf2_trsm_dev reads one strict triangle
-  PLE_RC(gf2_trsm_dev(&T11, &Y, 0, 0, s));                               // Y = L11^-1 (P B)[0, r)
+  GF2_RC(gf2_trsm_dev(&T11, &Y, 0, 0, s));                               // Y = L11^-1 (P B)[0, r)
   if (check && rank < m) {
     gf2_dmat C = win(*B, rank, 0, m - rank, kb), L = win(*A, rank, 0, m - rank, rank);
-    if (rank > 0) PLE_RC(gf2_mul_dev(&C, &L, &Y, 1, 0, 0, s));          // rows r.. of P B minus L21 Y: zero iff consistent
+    if (rank > 0) GF2_RC(gf2_mul_dev(&C, &L, &Y, 1, 0, 0, s));          // rows r.. of P B minus L21 Y: zero iff consistent
     DBuf flag;
-    PLE_RC(flag.alloc(sizeof(int)));
+    GF2_RC(flag.alloc(sizeof(int)));
     int h = 0;
-    PLE_TRY(hipMemsetAsync(flag.p, 0, sizeof(int), s));
-    PLE_TRY(gf2k_any_nonzero(static_cast<const u64 *>(B->data), B->ld, rank, m, kb, flag.as<int>(), s));
-    PLE_TRY(hipMemcpyAsync(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    PLE_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(int), s));
+    HIP_TRY(gf2k_any_nonzero(static_cast<const u64 *>(B->data), B->ld, rank, m, kb, flag.as<int>(), s));
+    HIP_TRY(hipMemcpyAsync(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     *inconsistent = h != 0;
   }
-  PLE_RC(gf2_trsm_dev(&T11, &Y, 1, 0, s));                               // Z = U11^-1 Y, free variables 0
+  GF2_RC(gf2_trsm_dev(&T11, &Y, 1, 0, s));                               // Z = U11^-1 Y, free variables 0
   if (B->nrows > rank) {
     hipLaunchKernelGGL(ple_gather, dim3(grid_of((long long)(B->nrows - rank) * bw, 256)), dim3(256), 0, s,
                        static_cast<u64 *>(B->data) + (long long)rank * B->ld, B->ld, (const u64 *)nullptr, 0ll, (const int *)nullptr,
                        B->nrows - rank, bw, bmask);
-    PLE_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
   }
   gf2_dmat Bn = win(*B, 0, 0, n, kb);
   return apply_rows(Bn, perm_map(Q, n, n, true), s);                     // X = Q^T Z (synchronous)

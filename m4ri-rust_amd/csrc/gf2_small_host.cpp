@@ -6,7 +6,7 @@
 // below M4RI_HIP_HOST_SMALL_WORK word operations (default 2^20; 0 = everything goes to the device, which is what the GPU
 // parity tests run with) mzd_mul / mzd_mul_m4rm / mzd_mul_naive / _mzd_mul_naive / _mzd_mul_va and mzd_echelonize* take the
 // routines below.  This is a dispatch, not a fallback: the entry points still require a usable HIP device and fail loudly
-// without one (m4ri_hip_api.cpp), and nothing here is used by bench.py or by any device-resident call.
+// without one (m4ri_hip_api.cpp, elim_host.cpp), and nothing here is used by bench.py or by any device-resident call.
 // The code is this library's own (word-parallel Four Russians on byte-aligned chunks / row XOR by set bits / word-parallel
 // Gauss-Jordan); it shares nothing with oracle/, which is test infrastructure.
 #include <cstdlib>

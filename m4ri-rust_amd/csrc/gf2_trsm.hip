@@ -152,16 +152,6 @@ inline int words_of(long long bits) { return (int)((bits + 63) >> 6); }
 inline u64 last_mask(long long bits) { return (bits & 63) ? ((1ull << (bits & 63)) - 1) : ~0ull; }
 inline long long even_ld(long long w) { return (w + 1) & ~1ll; }
 
-#define TRSM_TRY(expr)                                    \
-  do {                                                    \
-    hipError_t _e = (expr);                               \
-    if (_e != hipSuccess) return gf2_fail_hip(_e, #expr); \
-  } while (0)
-#define TRSM_RC(expr)    \
-  do {                   \
-    int _rc = (expr);    \
-    if (_rc) return _rc; \
-  } while (0)
 
 inline gf2_dmat win(const gf2_dmat &A, long long r, long long c, int rows, int cols) {  // c: multiple of 64
   return gf2_dmat{static_cast<u64 *>(A.data) + r * A.ld + (c >> 6), A.ld, rows, cols};
@@ -193,11 +183,11 @@ int leaf(const TrsmCtx &c, int b) {
   gf2_dmat I{c.inv + (long long)b * c.d * c.ldi, c.ldi, nr, nr};
   gf2_dmat X = c.right ? win(c.B, 0, r, c.B.nrows, nr) : win(c.B, r, 0, nr, c.B.ncols);
   gf2_dmat S{c.tmp, c.ldt, X.nrows, X.ncols};
-  TRSM_RC(c.right ? gf2_mul_dev(&S, &X, &I, 0, 0, 0, c.s) : gf2_mul_dev(&S, &I, &X, 0, 0, 0, c.s));
+  GF2_RC(c.right ? gf2_mul_dev(&S, &X, &I, 0, 0, 0, c.s) : gf2_mul_dev(&S, &I, &X, 0, 0, 0, c.s));
   const int words = words_of(X.ncols);
   hipLaunchKernelGGL(trsm_copy_back, dim3((unsigned)(((long long)X.nrows * words + 255) / 256)), dim3(256), 0, c.s,
                      static_cast<u64 *>(X.data), X.ld, c.tmp, c.ldt, X.nrows, words, last_mask(X.ncols));
-  TRSM_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return 0;
 }
 
@@ -208,24 +198,24 @@ int solve(const TrsmCtx &c, int b0, int b1) {
   const int r = b0 * c.d, rm = mid * c.d, h1 = rm - r, h2 = std::min(c.n, b1 * c.d) - rm;
   // the half solved first: the one no other block of the triangle feeds into
   const bool first_low = c.right ? c.upper : !c.upper;
-  TRSM_RC(first_low ? solve(c, b0, mid) : solve(c, mid, b1));
+  GF2_RC(first_low ? solve(c, b0, mid) : solve(c, mid, b1));
   if (!c.right) {
     const int k = c.B.ncols;
     if (first_low) {  // B2 ^= T21 X1
       gf2_dmat C = win(c.B, rm, 0, h2, k), A = win(c.T, rm, r, h2, h1), X = win(c.B, r, 0, h1, k);
-      TRSM_RC(gf2_mul_dev(&C, &A, &X, 1, 0, 0, c.s));
+      GF2_RC(gf2_mul_dev(&C, &A, &X, 1, 0, 0, c.s));
     } else {  // B1 ^= T12 X2
       gf2_dmat C = win(c.B, r, 0, h1, k), A = win(c.T, r, rm, h1, h2), X = win(c.B, rm, 0, h2, k);
-      TRSM_RC(gf2_mul_dev(&C, &A, &X, 1, 0, 0, c.s));
+      GF2_RC(gf2_mul_dev(&C, &A, &X, 1, 0, 0, c.s));
     }
   } else {
     const int k = c.B.nrows;
     if (first_low) {  // B2 ^= X1 T12
       gf2_dmat C = win(c.B, 0, rm, k, h2), X = win(c.B, 0, r, k, h1), A = win(c.T, r, rm, h1, h2);
-      TRSM_RC(gf2_mul_dev(&C, &X, &A, 1, 0, 0, c.s));
+      GF2_RC(gf2_mul_dev(&C, &X, &A, 1, 0, 0, c.s));
     } else {  // B1 ^= X2 T21
       gf2_dmat C = win(c.B, 0, r, k, h1), X = win(c.B, 0, rm, k, h2), A = win(c.T, rm, r, h2, h1);
-      TRSM_RC(gf2_mul_dev(&C, &X, &A, 1, 0, 0, c.s));
+      GF2_RC(gf2_mul_dev(&C, &X, &A, 1, 0, 0, c.s));
     }
   }
   return first_low ? solve(c, mid, b1) : solve(c, b0, mid);
@@ -253,9 +243,9 @@ extern "C" int gf2_trsm_dev(gf2_dmat const *T, gf2_dmat *B, int upper, int right
   const size_t tmp_rows = right ? (size_t)B->nrows : (size_t)d;
   std::lock_guard<std::mutex> lk(g_trsm_mu);
   void *p = nullptr;
-  TRSM_RC(gf2_stream_scratch(s, (size_t)nb * d * c.ldi * 8, &p, 4));
+  GF2_RC(gf2_stream_scratch(s, (size_t)nb * d * c.ldi * 8, &p, 4));
   c.inv = static_cast<u64 *>(p);
-  TRSM_RC(gf2_stream_scratch(s, tmp_rows * c.ldt * 8, &p, 5));
+  GF2_RC(gf2_stream_scratch(s, tmp_rows * c.ldt * 8, &p, 5));
   c.tmp = static_cast<u64 *>(p);
   const size_t lds_bytes = (size_t)2 * d * (d >> 6) * 8;  // 64 KiB at d = 512
   if (upper)
@@ -264,6 +254,6 @@ extern "C" int gf2_trsm_dev(gf2_dmat const *T, gf2_dmat *B, int upper, int right
   else
     hipLaunchKernelGGL(trsm_invert_blocks<false>, dim3(nb), dim3(d), lds_bytes, s, static_cast<const u64 *>(T->data), (long long)T->ld, n,
                        d, c.inv, c.ldi);
-  TRSM_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return solve(c, 0, nb);
 }

@@ -1,5 +1,5 @@
 """The launch planner's time model against the clock: `pick_levels` / `plan_tiles` choose Strassen level
-counts and tile variants by MODELLED time (m4ri-rust_amd/csrc/m4ri_hip_api.cpp: level_time_model), with constants fitted on
+counts and tile variants by MODELLED time (m4ri-rust_amd/csrc/mul_plan_host.cpp: level_time_model), with constants fitted on
 measurements.  In round 3 the single-level plan ran 2.1 x above its model (unpacked A leaves) and nothing noticed; this test
 holds every (shape, level count) of a small sweep to the model, so that a plan the planner is asked to price cannot drift that
 far again.  Reference entry points behind it: mzd_mul (m4ri-sys/src/strassen.rs:8-18), mzd_mul_m4rm (brilliantrussian.rs:210-216)."""

@@ -27,7 +27,7 @@ DESCRIPTIONS = {
     "M4RI_HIP_HOST_PIPELINE_BLOCKS": "row blocks of the host upload / multiply / download pipeline (default 4; < 2 switches it off)",
     "M4RI_HIP_APACK": "0: Strassen leaves of A stay row-major (no row-group-packed layout)",
     "M4RI_HIP_PLAIN_APACK": "0: plain products never pack A first",
-    "M4RI_HIP_RESULT_SIDE_COLS": "a product into a NULL destination with at most this many columns (default 8) and >= 1 MiB of rows also comes back in its packed transposed form, from which mzd_transpose of that product is served (INTEGRATION 4b, 4d); 0 = never",
+    "M4RI_HIP_RESULT_SIDE_COLS": "a product into a NULL destination with at most this many columns and >= 1 MiB of rows also comes back in its packed transposed form, from which mzd_transpose of that product is served (INTEGRATION 4b, 4d); 0 = never (default: opt-in, as `gf2_set_result_side_cols`)",
     "M4RI_HIP_ELIM_LOOKAHEAD": "0: the pivot search of an elimination step runs as its own launch instead of on an extra workgroup of the previous step's update launch (DESIGN 7.1)",
     "M4RI_HIP_ELIM_SPECULATE": "0: the trailing product of an elimination block waits for the block's record instead of being enqueued ahead of it",
     "M4RI_HIP_KERNEL_CENSUS_FILE": "path: the launch counts of the process (gf2_kernel_census) are appended to this file when the library is unloaded; the GPU test suite sets it so that kernels launched by its child processes count (tests/test_zz_kernel_census.py)",
