@@ -416,6 +416,11 @@ int gf2_host_plan_model(int m, int l, int n, int algo, int param, double t_end[1
  * suite ends with a test that every kernel the shared object contains has been launched (tests/test_zz_kernel_census.py). */
 size_t gf2_kernel_census(char *buf, size_t cap);
 
+/* Where the library's device memory came from so far (scratch, the device copies of host operands, gf2_dmat_alloc): out[0] = requests
+ * served from the block cache, out[1] = requests served by a fresh hipMalloc.  Read-only; tests/dirty_pool.py uses it to prove that a
+ * call ran on blocks it had filled beforehand. */
+void gf2_dev_alloc_counts(long long out[2]);
+
 #ifdef __cplusplus
 }
 #endif

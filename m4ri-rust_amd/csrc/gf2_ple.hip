@@ -248,21 +248,13 @@ inline long long even_ld(long long w) { return (w + 1) & ~1ll; }  // device matr
 inline unsigned grid_of(long long n, int b) { return (unsigned)((n + b - 1) / b); }
 
 
-struct DBuf {
-  void *p = nullptr;
-  int alloc(size_t bytes) {
-    hipError_t e = hipMalloc(&p, bytes ? bytes : 8);
-    if (e != hipSuccess) {
-      p = nullptr;
-      return gf2_fail_hip(e, "gf2_ple: hipMalloc");
-    }
-    return 0;
+// Scratch of this file comes from the block cache (DevBuf), whose free is not stream-ordered: a scope that holds such a block ends
+// behind a wait for its stream on every path, the error returns included.  Declared after the buffers, so destroyed before them.
+struct DrainOnExit {
+  hipStream_t s;
+  ~DrainOnExit() {
+    if (hipStreamSynchronize(s) != hipSuccess) (void)hipGetLastError();
   }
-  ~DBuf() {
-    if (p) (void)hipFree(p);
-  }
-  template <class T>
-  T *as() const { return static_cast<T *>(p); }
 };
 
 inline gf2_dmat win(const gf2_dmat &A, long long r, long long c, int rows, int cols) {
@@ -373,7 +365,8 @@ std::vector<int> perm_map(const int *P, int len, int rows, bool descending) {
 int apply_rows(const gf2_dmat &A, const std::vector<int> &map, hipStream_t s) {
   const int rows = A.nrows, words = words_of(A.ncols);
   if (rows == 0 || words == 0) return 0;
-  DBuf dm, sc;
+  DevBuf dm, sc;
+  DrainOnExit drain{s};
   GF2_RC(dm.alloc((size_t)rows * sizeof(int)));
   GF2_RC(sc.alloc((size_t)rows * words * 8));
   HIP_TRY(hipMemcpyAsync(dm.p, map.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice, s));
@@ -389,7 +382,8 @@ static int apply_cols_dev(const gf2_dmat &A, const std::vector<int> &map, hipStr
   const int m = A.nrows, n = A.ncols;
   if (m == 0 || n == 0) return 0;
   const long long tw = even_ld(words_of(m)), aw = even_ld(words_of(n));
-  DBuf t1, t2, dm;
+  DevBuf t1, t2, dm;
+  DrainOnExit drain{s};
   GF2_RC(t1.alloc((size_t)std::max<long long>((long long)n * tw, (long long)m * aw) * 8));
   GF2_RC(t2.alloc((size_t)n * tw * 8));
   GF2_RC(dm.alloc((size_t)n * sizeof(int)));
@@ -452,7 +446,8 @@ extern "C" int gf2_ple_dev(gf2_dmat *A, int pluq, int *P, int *Q, int *rank, voi
   if (A->ld < words_of(n)) return gf2_fail_msg("gf2_ple_dev: row stride smaller than row width");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int aw = words_of(n);
-  DBuf pi, qc, sc, cand, tab;
+  DevBuf pi, qc, sc, cand, tab, stash, eb;
+  DrainOnExit drain{s};
   GF2_RC(pi.alloc((size_t)m * sizeof(int)));
   GF2_RC(qc.alloc((size_t)std::min(m, n) * sizeof(int)));
   const long long swords = std::max<long long>((long long)m * ((aw + 1) / 2), (long long)m * (words_of(std::min(m, n)) + 1));
@@ -463,7 +458,6 @@ extern "C" int gf2_ple_dev(gf2_dmat *A, int pluq, int *P, int *Q, int *rank, voi
   HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&rank_host), 8, 0));
   int depth = 1;
   for (int w = aw; w > 1; w = (w + 1) / 2) ++depth;  // levels of the column recursion
-  DBuf stash;
   GF2_RC(stash.alloc((size_t)depth * m * sizeof(int)));
   PleCtx c{*A, m, n, s, pi.as<int>(), qc.as<int>(), {}, sc.as<u64>(), cand.as<int>(), tab.as<u64>(), rank_host};
   for (int d = 0; d < depth; ++d) c.stash.push_back(stash.as<int>() + (size_t)d * m);
@@ -486,7 +480,6 @@ extern "C" int gf2_ple_dev(gf2_dmat *A, int pluq, int *P, int *Q, int *rank, voi
   if (pluq && r > 0) {
     // U = E with the transpositions of Q applied to its columns in ascending order (mzd_apply_p_right_trans); the bits of E below
     // the diagonal are zero, so the swaps that would touch L are no-ops and the whole rows can be permuted
-    DBuf eb;
     const long long eld = even_ld(aw);
     GF2_RC(eb.alloc((size_t)r * eld * 8));
     gf2_dmat E{eb.as<u64>(), eld, r, n};
@@ -526,7 +519,8 @@ extern "C" int gf2_pluq_solve_left_dev(gf2_dmat const *A, int rank, const int *P
   if (check && rank < m) {
     gf2_dmat C = win(*B, rank, 0, m - rank, kb), L = win(*A, rank, 0, m - rank, rank);
     if (rank > 0) GF2_RC(gf2_mul_dev(&C, &L, &Y, 1, 0, 0, s));          // rows r.. of P B minus L21 Y: zero iff consistent
-    DBuf flag;
+    DevBuf flag;
+    DrainOnExit drain{s};
     GF2_RC(flag.alloc(sizeof(int)));
     int h = 0;
     HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(int), s));

@@ -128,6 +128,8 @@ struct DevPool {
   size_t cached = 0;
 };
 DevPool g_pools[16];
+// how gf2_dev_alloc served its requests so far: [0] from the block cache, [1] by a fresh hipMalloc (gf2_dev_alloc_counts)
+std::atomic<long long> g_alloc_counts[2];
 
 size_t round_size(size_t b) {
   const size_t g = b < ((size_t)64 << 20) ? ((size_t)1 << 20) : ((size_t)64 << 20);
@@ -190,6 +192,7 @@ int gf2_dev_alloc(void **p, size_t bytes) {
       *p = it->second;
       pool.cached -= it->first;
       pool.free_.erase(it);
+      g_alloc_counts[0].fetch_add(1, std::memory_order_relaxed);
       return 0;
     }
   }
@@ -205,7 +208,14 @@ int gf2_dev_alloc(void **p, size_t bytes) {
   }
   if (e != hipSuccess) return gf2_fail_hip(e, "hipMalloc");
   remember_owner(*p, dev);
+  g_alloc_counts[1].fetch_add(1, std::memory_order_relaxed);
   return 0;
+}
+
+// out[0]: requests gf2_dev_alloc has served from the block cache, out[1]: by a fresh hipMalloc, since the library was loaded
+extern "C" void gf2_dev_alloc_counts(long long out[2]) {
+  out[0] = g_alloc_counts[0].load(std::memory_order_relaxed);
+  out[1] = g_alloc_counts[1].load(std::memory_order_relaxed);
 }
 
 // Hands a block back to the pool of the device that owns it.  NOT stream-ordered: the caller guarantees that no queued

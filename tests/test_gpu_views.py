@@ -9,12 +9,11 @@ Every case checks, bit for bit, against the oracle applied to a clean copy of ea
   its parent outside the window as it was;  4. source windows and their parents are unchanged;  5. the kernel family the case is
   meant for ran (launch census before and after the call), so that a moved threshold fails the case instead of re-routing it.
 Shapes were picked with the shipped planner (gf2_tile_plan, gf2_mul_plan; plain_path's thresholds for the thin products)."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import gf2util as g
+from census_util import assert_route, census
 
 pytestmark = pytest.mark.gpu
 
@@ -27,26 +26,6 @@ def pkg(built):
     from m4ri_rust_amd import device
     device.require_gpu()
     return p
-
-
-# ---- launch census ----------------------------------------------------------------------------------
-
-def census(L):
-    need = L.gf2_kernel_census(None, 0)
-    buf = ctypes.create_string_buffer(need + 1)
-    L.gf2_kernel_census(buf, need + 1)
-    out = {}
-    for ln in buf.value.decode().splitlines():
-        parts = ln.split(None, 1)
-        if len(parts) == 2 and parts[0].isdigit():
-            out[parts[1].strip()] = out.get(parts[1].strip(), 0) + int(parts[0])
-    return out
-
-
-def assert_route(before, after, families):
-    ran = sorted(k for k, v in after.items() if v > before.get(k, 0))
-    for f in families:
-        assert any(f in k for k in ran), "route check: no %s kernel ran (launched: %s)" % (f, ran)
 
 
 # ---- operands ----------------------------------------------------------------------------------------
