@@ -189,7 +189,15 @@ mzd_t *mzd_kernel_left_pluq(mzd_t *A, int cutoff);
 /* ===================================================================================== */
 
 /* A dense bit matrix in device memory: row-major 64-bit words, LSB-first, `ld` words between
- * rows (ld even, base 16-byte aligned), excess bits of the last word zero. */
+ * rows (ld even, base 16-byte aligned), excess bits of the last word zero.
+ * Two size limits lie above the shapes callers usually have; both are tested past them, bit for bit (tests/test_gpu_limits.py):
+ *  - more than 65 536 x 64 = 4 194 304 rows or columns: gf2_transpose_dev, mzd_transpose, gf2_mul_nt_dev and the products that
+ *    transpose B put one workgroup per 64 rows into the y dimension of a launch.  The HIP runtime accepts gridDim.y = 65 538 on this
+ *    part (measured: 4 194 369 rows), and so do the row-parallel products, the elimination and gf2_solve_left_dev;
+ *  - operands larger than 4 GiB (tested: 9 000 001 x 4096 and 36 929 x 1 048 640): every entry of this section addresses rows with
+ *    64-bit offsets.  The tile kernel alone carries 32-bit byte counts: gf2_mul_dev does not make its packed copy of an A of 4 GiB and
+ *    more (it reads A in place), and returns -1 with "row stride too large for the tile kernel" for rows of more than about 8 million
+ *    columns instead of launching.  nrows and ncols are ints: a dimension stays below 2^31. */
 typedef struct {
   uint64_t *data; /* device pointer */
   int64_t ld;     /* words per row stride */
