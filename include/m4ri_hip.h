@@ -189,7 +189,9 @@ mzd_t *mzd_kernel_left_pluq(mzd_t *A, int cutoff);
 /* ===================================================================================== */
 
 /* A dense bit matrix in device memory: row-major 64-bit words, LSB-first, `ld` words between
- * rows (ld even, base 16-byte aligned), excess bits of the last word zero.
+ * rows (ld even, base 16-byte aligned), excess bits of the last word zero.  Entries that say "accepts 8-byte-aligned rows" also take
+ * views with an odd `ld` or a base at an odd word; the elimination-family entries (echelonize, inverse, ple, apply_p, trsm, solve,
+ * nullspace) keep the rule in the parentheses.
  * Two size limits lie above the shapes callers usually have; both are tested past them, bit for bit (tests/test_gpu_limits.py):
  *  - more than 65 536 x 64 = 4 194 304 rows or columns: gf2_transpose_dev, mzd_transpose, gf2_mul_nt_dev and the products that
  *    transpose B put one workgroup per 64 rows into the y dimension of a launch.  The HIP runtime accepts gridDim.y = 65 538 on this
@@ -226,15 +228,55 @@ int gf2_dmat_fill_random_rows(gf2_dmat *M, uint64_t seed, int64_t row0, void *st
 /* general block: rows [row0, ..) x words [col_word0, ..) of a seeded matrix with full_ncols columns (column-panel shards) */
 int gf2_dmat_fill_random_block(gf2_dmat *M, uint64_t seed, int64_t row0, int64_t col_word0, int full_ncols, void *stream);
 
+/* --- Arguments and aliasing of the entries below (gf2_mul_dev ... gf2_nullspace_dev) ---
+ * Every argument is checked before a device is required and before the first HIP call, so a bad call fails the same way with and
+ * without a device: a null struct pointer, a null `data` on a non-empty matrix, a null required out-pointer (`equal`, `singular`,
+ * `rank`, `inconsistent`), a negative dimension, an `ld` below the row width, a `data` that is not 8-byte aligned and a shape
+ * mismatch return -1 and set gf2_last_error to a text that starts with the entry's name; nothing is launched, allocated or written.
+ * Empty shapes return 0 without a launch and without needing a device.  The aliasing check comes last.
+ *
+ * THE RULE: a matrix that a call writes may share no word with any other matrix argument of that call, except where listed below.
+ * Matrices that are only read may be one matrix or overlap freely.  A call that breaks the rule returns -1 ("overlap" in
+ * gf2_last_error) before anything is launched.  "Share a word" is decided as for the block calls further down, on whole words: with
+ * equal `ld` the two word rectangles are compared exactly, so two column ranges of one parent are fine; with different `ld` any
+ * intersection of the address ranges counts.
+ *
+ * | entry | allowed aliasing | refused (-1, "overlap") |
+ * |---|---|---|
+ * | `gf2_mul_dev`, `gf2_mul_nt_dev` | A is B / Bt; A and B overlapping; C, A, B three disjoint column ranges of one parent | C sharing a word with A or B (with or without `accumulate`) |
+ * | `gf2_add_dev` | C identical to A, to B, or to both (same `data`, `ld`, shape); A is B | C sharing a word with A or B in any other way (shifted by a row, a word, another `ld`) |
+ * | `gf2_transpose_dev` | D and S disjoint column ranges of one parent | D sharing a word with S, the square "in place" case included |
+ * | `gf2_equal_dev` | anything; A is B gives `*equal = 1` | – |
+ * | `gf2_inverse_dev` | Ainv identical to A, or overlapping it in any way (A is copied out before Ainv is written; say so) | – |
+ * | `gf2_trsm_dev` | – | B sharing a word with T |
+ * | `gf2_solve_left_dev`, `gf2_pluq_solve_left_dev` | – | B sharing a word with A |
+ *
+ * gf2_inverse_batch_dev keeps its own, stricter rule (stated at its declaration); gf2_copy_block_dev, gf2_submatrix_dev, gf2_concat_dev
+ * and gf2_stack_dev state theirs in the paragraph above them; gf2_nullspace_dev allocates K itself, so K cannot alias A. */
+
 /* C (+)= A*B on `stream` (hipStream_t, NULL = default stream); asynchronous.
- * algo: GF2_ALGO_*; param: Strassen levels when algo==STRASSEN (0 = automatic), else ignored. */
+ * algo: GF2_ALGO_*; param: Strassen levels when algo==STRASSEN (0 = automatic), else ignored.
+ * Aliasing: A and B are only read -- A may be B (squaring) and the two may overlap; C is stored tile by tile while other workgroups
+ * still read those rows of A and B, so C may share no word with either, with or without `accumulate` (-1, "overlap").  C, A and B may
+ * be three disjoint column ranges of one parent.  Accepts 8-byte-aligned rows (an odd `ld` takes the plain path instead of Strassen).
+ * An empty C returns 0; an inner dimension of 0 clears C (accumulate: leaves it). */
 int gf2_mul_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *B, int accumulate, int algo, int param,
                 void *stream);
-/* C (+)= A * Bt^T (row-parity form, mzd.rs:154-168) */
+/* C (+)= A * Bt^T (row-parity form, mzd.rs:154-168).  Aliasing as gf2_mul_dev: A may be Bt (the Gram matrix A A^T) or overlap it; C
+ * may share no word with A or Bt.  Accepts 8-byte-aligned rows. */
 int gf2_mul_nt_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *Bt, int accumulate, void *stream);
-/* C = A xor B (mzd.rs:223), D = S^T (mzd.rs:148), equality (mzd.rs:187; *equal = 1/0) */
+/* C = A xor B (mzd.rs:223).  Aliasing: C may be identical to A, to B, or to both (same `data`, `ld` and shape: mzd_add(A, A, B), the
+ * reference's +=; every word is read and written by the one thread that owns it), and A may be B (the result is zero).  A C that shares
+ * a word with A or B in any other way -- shifted by a row or a word, the same base under another `ld` -- returns -1 ("overlap").
+ * Accepts 8-byte-aligned rows: the kernel uses 16-byte accesses only when all three `ld` are even and all three bases 16-byte aligned,
+ * and 8-byte accesses otherwise. */
 int gf2_add_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *B, void *stream);
+/* D = S^T (mzd.rs:148).  Aliasing: D may share no word with S (-1, "overlap"): there is no in-place transposition, not for a square
+ * matrix either; D and S may be disjoint column ranges of one parent.  Accepts 8-byte-aligned rows (both kernels read and write caller
+ * memory one 8-byte word at a time). */
 int gf2_transpose_dev(gf2_dmat *D, gf2_dmat const *S, void *stream);
+/* equality (mzd.rs:187; *equal = 1/0; different shapes: 0; two empty matrices of one shape: 1 without a launch).  Both matrices are only
+ * read, so any aliasing is allowed: A is B gives *equal = 1.  Accepts 8-byte-aligned rows (8-byte reads).  Synchronous. */
 int gf2_equal_dev(gf2_dmat const *A, gf2_dmat const *B, int *equal, void *stream);
 /* Assembly on the device.  The four calls below move bits between ANY bit offsets; destinations are caller-allocated and may be views in
  * a larger buffer.  Every argument is checked before the first HIP call: a destination of the wrong shape, a rectangle that leaves S or
@@ -259,7 +301,9 @@ int gf2_stack_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *B, void *strea
  * the row operations (augmented systems).  *rank receives the rank, pivot_cols (host, may be NULL, >= min(rows, limit)
  * ints) the pivot columns.  Synchronous. */
 int gf2_echelonize_dev(gf2_dmat *A, int full, int ncols_limit, int *rank, int *pivot_cols, void *stream);
-/* Ainv = A^-1 for square A; *singular = 1 (Ainv untouched) if A has no inverse.  Synchronous. */
+/* Ainv = A^-1 for square A; *singular = 1 (Ainv untouched) if A has no inverse.  Synchronous.  Aliasing: none refused -- A is copied
+ * into scratch [A | pad | I] before anything is written and Ainv is written from that scratch after the elimination, so Ainv may be
+ * identical to A (inversion in place; a singular A is then left unchanged) or overlap it in any way. */
 int gf2_inverse_dev(gf2_dmat *Ainv, gf2_dmat const *A, int *singular, void *stream);
 /* --- batched elimination of small matrices (contract per matrix: INTEGRATION.md section 3) ---
  * A batch is `batch` matrices of equal shape stored one below the other in one gf2_dmat: matrix b is rows [b*m, (b+1)*m), so
@@ -285,7 +329,7 @@ int gf2_elim_batch_plan(int m, int ncols, int inverse, long long out[4]);
  * further row of B is zero; *inconsistent = 1 when check != 0 and the system has no solution (B is then as mzd_solve_left leaves it).
  * A and B may be strided views: bits outside them do not change.  m, n or B.ncols equal to 0: returns 0, nothing is done.  A shape
  * error returns -1 and sets gf2_last_error (the host entry aborts instead).  Synchronous on `stream` (the rank must reach the host)
- * and ordered behind the work pending there. */
+ * and ordered behind the work pending there.  Aliasing: A and B are both written; B may share no word with A (-1, "overlap"). */
 int gf2_solve_left_dev(gf2_dmat *A, gf2_dmat *B, int check, int *inconsistent, void *stream);
 /* PLE (pluq = 0) or PLUQ (pluq = 1) of a device matrix in place, the layout of mzd_ple / mzd_pluq; P (nrows ints) and Q (ncols
  * ints) are HOST arrays that receive the transposition lists.  Synchronous. */
@@ -294,13 +338,15 @@ int gf2_ple_dev(gf2_dmat *A, int pluq, int *P, int *Q, int *rank, void *stream);
  * transposition list of len entries.  Synchronous. */
 int gf2_apply_p_dev(gf2_dmat *A, const int *P, int len, int right, int trans, void *stream);
 /* mzd_pluq_solve_left on the device: A as gf2_ple_dev(pluq = 1) left it, P / Q host arrays; B (max(nrows, ncols) rows or more)
- * receives X; *inconsistent = 1 when check != 0 finds the system inconsistent.  Synchronous. */
+ * receives X; *inconsistent = 1 when check != 0 finds the system inconsistent.  Synchronous.  Aliasing: B is rewritten step by step
+ * while A is still read; B may share no word with A (-1, "overlap"). */
 int gf2_pluq_solve_left_dev(gf2_dmat const *A, int rank, const int *P, const int *Q, gf2_dmat *B, int check, int *inconsistent,
                             void *stream);
 /* device-resident: B = T^-1 B (right == 0) or B T^-1 (right != 0); upper selects the triangle.  The contract of mzd_trsm_* above:
  * only the strict triangle of T is read, B's bits alone change (the excess bits of its last word stay zero; a view's neighbours stay
  * as they are).  A non-square T or a dimension mismatch returns -1 and sets gf2_last_error; n = 0 or an empty B returns 0 without a
- * launch.  Asynchronous on `stream`, like gf2_mul_dev: one launch inverts the diagonal blocks, the rest is products. */
+ * launch.  Asynchronous on `stream`, like gf2_mul_dev: one launch inverts the diagonal blocks, the rest is products.  Aliasing: T and B
+ * may be views of one buffer, but B may share no word with T (-1, "overlap"): its blocks are rewritten while later steps read T. */
 int gf2_trsm_dev(gf2_dmat const *T, gf2_dmat *B, int upper, int right, void *stream);
 /* Null space of a device matrix, the contract of mzd_kernel_left_pluq above: A (may be a strided view) is reduced in place to its
  * reduced row echelon form; *K is filled in by the call: n x (n - rank), allocated with gf2_dmat_alloc and freed by the caller with

@@ -12,42 +12,17 @@ namespace {
 
 inline long long words_of(long long bits) { return (bits + 63) >> 6; }
 
-int bad(const char *fn, const char *what) { return gf2_fail_msg((std::string(fn) + ": " + what).c_str()); }
+int bad(const char *fn, const char *what) { return gf2_bad_arg(fn, what); }
 
-// a matrix argument that can be addressed: `name` goes into the message
-int check_mat(const char *fn, const char *name, gf2_dmat const *M) {
-  if (!M) return bad(fn, (std::string(name) + " is null").c_str());
-  if (M->nrows < 0 || M->ncols < 0) return bad(fn, (std::string(name) + " has a negative dimension").c_str());
-  if (M->nrows > 0 && M->ncols > 0) {
-    if (!M->data) return bad(fn, (std::string(name) + ".data is null").c_str());
-    if (reinterpret_cast<uintptr_t>(M->data) & 7) return bad(fn, (std::string(name) + ".data is not 8-byte aligned").c_str());
-    if (M->ld < words_of(M->ncols)) return bad(fn, (std::string(name) + ".ld is smaller than the row width").c_str());
-  }
-  return 0;
-}
+int check_mat(const char *fn, const char *name, gf2_dmat const *M) { return gf2_check_mat(fn, name, M); }
 
-// Do the rectangles share a bit?  (Both are non-empty and lie inside their matrices.)  With one row stride a bit's address is
-// row * L + column (L = 64 * ld), whatever parent the two views were cut from, so the answer is exact: row i of S's rectangle is the
-// interval [i L, i L + ncols), row j of D's the interval [x + j L, x + j L + ncols) with x the distance of the rectangles' first
-// bits, and ncols <= L.  With different strides the word ranges of the two rectangles are compared: conservative.
+// Do the rectangles share a bit?  (Both are non-empty and lie inside their matrices.)  The rule is gf2_bit_rects_share's
+// (api_internal.h): exact with one row stride, by word range with two.
 bool rects_overlap(gf2_dmat const *D, long long dr, long long dc, gf2_dmat const *S, long long sr, long long sc, long long nrows,
                    long long ncols) {
   const __int128 s0 = (__int128)reinterpret_cast<uintptr_t>(S->data) * 8 + ((__int128)sr * S->ld) * 64 + sc;
   const __int128 d0 = (__int128)reinterpret_cast<uintptr_t>(D->data) * 8 + ((__int128)dr * D->ld) * 64 + dc;
-  if (S->ld == D->ld) {
-    const __int128 L = (__int128)S->ld * 64, x = d0 - s0;
-    __int128 e = x / L, f = x % L;
-    if (f < 0) {
-      f += L;
-      e -= 1;
-    }
-    // D's row j meets S's row i = j + e (distance f) or i = j + e + 1 (distance L - f)
-    const bool same = (e < nrows && -e < nrows) && f < ncols;
-    const bool next = (e + 1 < nrows && -(e + 1) < nrows) && L - f < ncols;
-    return same || next;
-  }
-  const __int128 s1 = s0 + ((__int128)(nrows - 1) * S->ld) * 64 + ncols - 1, d1 = d0 + ((__int128)(nrows - 1) * D->ld) * 64 + ncols - 1;
-  return (s0 >> 6) <= (d1 >> 6) && (d0 >> 6) <= (s1 >> 6);
+  return gf2_bit_rects_share(s0, S->ld, nrows, ncols, d0, D->ld, nrows, ncols);
 }
 
 // 0: go ahead; 1: nothing to do; -1: refused (gf2_last_error is set)

@@ -170,9 +170,12 @@ static int echelonize_dev(gf2_dmat *A, int full, int col_limit, int *rank_out, i
 }
 
 extern "C" int gf2_echelonize_dev(gf2_dmat *A, int full, int ncols_limit, int *rank, int *pivot_cols, void *stream) {
+  static const char fn[] = "gf2_echelonize_dev";
+  if (int rc = gf2_check_mat(fn, "A", A)) return rc;
+  if (!rank) return gf2_bad_arg(fn, "rank is null");
+  *rank = 0;
+  if (A->nrows == 0 || A->ncols == 0) return 0;
   if (int rc = gf2_require_device()) return rc;
-  if (!A || !A->data || !rank) return gf2_fail_msg("gf2_echelonize_dev: null argument");
-  if (A->ld < words_of(A->ncols)) return gf2_fail_msg("gf2_echelonize_dev: row stride smaller than row width");
   hipStream_t s = static_cast<hipStream_t>(stream);
   std::lock_guard<std::mutex> lk(gf2_enqueue_mu);
   return echelonize_dev(A, full, ncols_limit, rank, pivot_cols, nullptr, s);
@@ -211,13 +214,17 @@ static int inverse_dev(gf2_dmat *Ainv, const u64 *Adata, long long lda, bool a_o
 }
 
 extern "C" int gf2_inverse_dev(gf2_dmat *Ainv, gf2_dmat const *A, int *singular, void *stream) {
-  if (int rc = gf2_require_device()) return rc;
-  if (!Ainv || !A || !singular || !A->data || !Ainv->data) return gf2_fail_msg("gf2_inverse_dev: null argument");
+  static const char fn[] = "gf2_inverse_dev";
+  if (gf2_check_mat(fn, "Ainv", Ainv) || gf2_check_mat(fn, "A", A)) return -1;
+  if (!singular) return gf2_bad_arg(fn, "singular is null");
   if (A->nrows != A->ncols || Ainv->nrows != A->nrows || Ainv->ncols != A->ncols)
-    return gf2_fail_msg("gf2_inverse_dev: matrices must be square and of equal size");
-  hipStream_t s = static_cast<hipStream_t>(stream);
+    return gf2_bad_arg(fn, "matrices must be square and of equal size");
   *singular = 0;
   if (A->nrows == 0) return 0;
+  // no aliasing rule: inverse_dev copies A into its scratch [A | pad | I] before anything is written, and writes Ainv from that
+  // scratch when the elimination is over, so Ainv may be A or overlap it in any way
+  if (int rc = gf2_require_device()) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
   std::lock_guard<std::mutex> lk(gf2_enqueue_mu);
   return inverse_dev(Ainv, A->data, A->ld, false, A->nrows, singular, s);
 }
@@ -378,7 +385,10 @@ extern "C" int gf2_solve_left_dev(gf2_dmat *A, gf2_dmat *B, int check, int *inco
   if (!A->data || !B->data) return gf2_fail_msg("gf2_solve_left_dev: null argument (A.data or B.data)");
   const int nw = words_of(n), bw = words_of(kb);
   if (A->ld < nw || B->ld < bw) return gf2_fail_msg("gf2_solve_left_dev: row stride (A.ld or B.ld) smaller than row width");
+  if ((reinterpret_cast<uintptr_t>(A->data) | reinterpret_cast<uintptr_t>(B->data)) & 7)
+    return gf2_fail_msg("gf2_solve_left_dev: A.data or B.data is not 8-byte aligned");
   if ((long long)nw * 64 + kb > INT32_MAX) return gf2_fail_msg("gf2_solve_left_dev: A.ncols + B.ncols is too large");
+  if (int rc = gf2_refuse_overlap("gf2_solve_left_dev", "B", B, "A", A)) return rc;  // both are written
   if (int rc = gf2_require_device()) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   std::lock_guard<std::mutex> lk(gf2_enqueue_mu);

@@ -2369,15 +2369,18 @@ __global__ __launch_bounds__(256) void gf2_va_kernel(const u64 *__restrict__ A, 
 // streaming helpers
 // ---------------------------------------------------------------------------------------------
 
-// C = A ^ B over a rows x words region (mzd_add, mzd.rs:220-223); also copy (B == nullptr) and zero.
-__global__ __launch_bounds__(256) void gf2_xor2d_kernel(u64 *__restrict__ C, long long ldc, const u64 *A, long long lda,
-                                                        const u64 *B, long long ldb, int rows, int words) {
+// C = A ^ B over a rows x words region (mzd_add, mzd.rs:220-223); also copy (B == nullptr) and zero.  16-byte accesses where all
+// three rows allow them (`vec`: every ld even and every base 16-byte aligned, decided by gf2k_xor2d), 8-byte accesses otherwise: a
+// caller's view may start at an odd word or have an odd ld.  A thread reads the words it writes and no others, so C may be A or B
+// (gf2_add_dev in place; C carries no __restrict__ for that reason).
+__global__ __launch_bounds__(256) void gf2_xor2d_kernel(u64 *C, long long ldc, const u64 *A, long long lda, const u64 *B, long long ldb,
+                                                        int rows, int words, int vec) {
   const int pairs = (words + 1) >> 1;
   const long long total = (long long)rows * pairs;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
        idx += (long long)gridDim.x * blockDim.x) {
     const int r = (int)(idx / pairs), w = (int)(idx % pairs) * 2;
-    if (w + 1 < words) {
+    if (w + 1 < words && vec) {
       uint4 a = A ? *reinterpret_cast<const uint4 *>(A + (long long)r * lda + w) : make_uint4(0, 0, 0, 0);
       if (B) a = xor4(a, *reinterpret_cast<const uint4 *>(B + (long long)r * ldb + w));
       *reinterpret_cast<uint4 *>(C + (long long)r * ldc + w) = a;
@@ -2385,6 +2388,11 @@ __global__ __launch_bounds__(256) void gf2_xor2d_kernel(u64 *__restrict__ C, lon
       u64 a = A ? A[(long long)r * lda + w] : 0;
       if (B) a ^= B[(long long)r * ldb + w];
       C[(long long)r * ldc + w] = a;
+      if (w + 1 < words) {  // the pair's second word, for rows that are only 8-byte aligned
+        u64 b = A ? A[(long long)r * lda + w + 1] : 0;
+        if (B) b ^= B[(long long)r * ldb + w + 1];
+        C[(long long)r * ldc + w + 1] = b;
+      }
     }
   }
 }
@@ -3589,7 +3597,10 @@ extern "C" hipError_t gf2k_xor2d(u64 *C, long long ldc, const u64 *A, long long 
                                  int words, hipStream_t stream) {
   if (rows <= 0 || words <= 0) return hipSuccess;
   const long long total = (long long)rows * ((words + 1) / 2);
-  hipLaunchKernelGGL(gf2_xor2d_kernel, dim3(grid_for(total)), dim3(256), 0, stream, C, ldc, A, lda, B, ldb, rows, words);
+  // 16-byte accesses only where every operand allows them (an absent operand, null with ld 0, allows anything); the same decision
+  // gf2k_padcopy makes
+  const int vec = !((ldc | lda | ldb) & 1) && !(((uintptr_t)C | (uintptr_t)A | (uintptr_t)B) & 15);
+  hipLaunchKernelGGL(gf2_xor2d_kernel, dim3(grid_for(total)), dim3(256), 0, stream, C, ldc, A, lda, B, ldb, rows, words, vec);
   return hipGetLastError();
 }
 

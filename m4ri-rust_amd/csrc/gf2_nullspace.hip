@@ -133,12 +133,12 @@ struct EventPair {
 }  // namespace
 
 extern "C" int gf2_nullspace_dev(gf2_dmat *A, gf2_dmat *K, int *rank, int *pivot_cols, void *stream) {
-  if (gf2_device_count() <= 0) return gf2_fail_msg("gf2_nullspace_dev: no usable HIP device");
-  if (!A || !K || !rank) return gf2_fail_msg("gf2_nullspace_dev: null argument");
-  if (A->nrows < 0 || A->ncols < 0) return gf2_fail_msg("gf2_nullspace_dev: negative dimension");
-  const int m = A->nrows, n = A->ncols, nw = words_of(n);
-  if (m > 0 && n > 0 && !A->data) return gf2_fail_msg("gf2_nullspace_dev: null argument");
-  if (m > 0 && A->ld < nw) return gf2_fail_msg("gf2_nullspace_dev: row stride smaller than row width");
+  static const char fn[] = "gf2_nullspace_dev";
+  if (int rc = gf2_check_mat(fn, "A", A)) return rc;
+  if (!K) return gf2_bad_arg(fn, "K is null");
+  if (!rank) return gf2_bad_arg(fn, "rank is null");
+  const int n = A->ncols, nw = words_of(n);
+  if (n > 0 && gf2_device_count() <= 0) return gf2_bad_arg(fn, "no usable HIP device");
   hipStream_t s = static_cast<hipStream_t>(stream);
   *rank = 0;
   *K = gf2_dmat{nullptr, 0, n, 0};

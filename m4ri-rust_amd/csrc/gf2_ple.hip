@@ -403,18 +403,18 @@ static int apply_cols_dev(const gf2_dmat &A, const std::vector<int> &map, hipStr
 }
 
 extern "C" int gf2_apply_p_dev(gf2_dmat *A, const int *P, int len, int right, int trans, void *stream) {
-  if (gf2_device_count() <= 0) return gf2_fail_msg("gf2_apply_p_dev: no usable HIP device");
-  if (!A || (!A->data && A->nrows && A->ncols) || (len > 0 && !P) || len < 0) return gf2_fail_msg("gf2_apply_p_dev: null argument");
+  static const char fn[] = "gf2_apply_p_dev";
+  if (int rc = gf2_check_mat(fn, "A", A)) return rc;
+  if (len < 0) return gf2_bad_arg(fn, "len is negative");
+  if (len > 0 && !P) return gf2_bad_arg(fn, "P is null");
+  for (int i = 0, n = std::min(len, right ? A->ncols : A->nrows); i < n; ++i)
+    if (P[i] < 0 || P[i] >= (right ? A->ncols : A->nrows)) return gf2_bad_arg(fn, "P[i] out of range");
+  if (A->nrows == 0 || A->ncols == 0) return 0;
+  if (gf2_device_count() <= 0) return gf2_bad_arg(fn, "no usable HIP device");
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (!right) {  // left: ascending swaps; left_trans: descending
-    const int n = std::min(len, A->nrows);
-    for (int i = 0; i < n; ++i)
-      if (P[i] < 0 || P[i] >= A->nrows) return gf2_fail_msg("gf2_apply_p_dev: P[i] out of range");
     return apply_rows(*A, perm_map(P, len, A->nrows, trans != 0), s);
   }
-  const int n = std::min(len, A->ncols);
-  for (int i = 0; i < n; ++i)
-    if (P[i] < 0 || P[i] >= A->ncols) return gf2_fail_msg("gf2_apply_p_dev: P[i] out of range");
   // right: column swaps descending; right_trans: ascending.  Column c of the result = column map[c] of the input.
   return apply_cols_dev(*A, perm_map(P, len, A->ncols, trans == 0), s);
 }
@@ -435,15 +435,16 @@ static void sigma_to_transpositions(const std::vector<int> &sigma, int *P) {
 }
 
 extern "C" int gf2_ple_dev(gf2_dmat *A, int pluq, int *P, int *Q, int *rank, void *stream) {
-  if (gf2_device_count() <= 0) return gf2_fail_msg("gf2_ple_dev: no usable HIP device");
-  if (!A || !rank || (A->nrows && !P) || (A->ncols && !Q)) return gf2_fail_msg("gf2_ple_dev: null argument");
+  static const char fn[] = "gf2_ple_dev";
+  if (int rc = gf2_check_mat(fn, "A", A)) return rc;
+  if (!rank) return gf2_bad_arg(fn, "rank is null");
+  if ((A->nrows && !P) || (A->ncols && !Q)) return gf2_bad_arg(fn, "P or Q is null");
   const int m = A->nrows, n = A->ncols;
   *rank = 0;
   for (int i = 0; i < m; ++i) P[i] = i;
   for (int j = 0; j < n; ++j) Q[j] = j;
   if (m == 0 || n == 0) return 0;
-  if (!A->data) return gf2_fail_msg("gf2_ple_dev: null argument");
-  if (A->ld < words_of(n)) return gf2_fail_msg("gf2_ple_dev: row stride smaller than row width");
+  if (gf2_device_count() <= 0) return gf2_bad_arg(fn, "no usable HIP device");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int aw = words_of(n);
   DevBuf pi, qc, sc, cand, tab, stash, eb;
@@ -497,9 +498,10 @@ extern "C" int gf2_ple_dev(gf2_dmat *A, int pluq, int *P, int *Q, int *rank, voi
 
 extern "C" int gf2_pluq_solve_left_dev(gf2_dmat const *A, int rank, const int *P, const int *Q, gf2_dmat *B, int check,
                                        int *inconsistent, void *stream) {
-  if (gf2_device_count() <= 0) return gf2_fail_msg("gf2_pluq_solve_left_dev: no usable HIP device");
-  if (!A || !B || !inconsistent || (A->nrows && !P) || (A->ncols && !Q))
-    return gf2_fail_msg("gf2_pluq_solve_left_dev: null argument");
+  static const char fn[] = "gf2_pluq_solve_left_dev";
+  if (gf2_check_mat(fn, "A", A) || gf2_check_mat(fn, "B", B)) return -1;
+  if (!inconsistent) return gf2_bad_arg(fn, "inconsistent is null");
+  if ((A->nrows && !P) || (A->ncols && !Q)) return gf2_bad_arg(fn, "P or Q is null");
   const int m = A->nrows, n = A->ncols, kb = B->ncols;
   *inconsistent = 0;
   if (B->nrows < m || B->nrows < n) return gf2_fail_msg("gf2_pluq_solve_left_dev: B needs max(A nrows, A ncols) rows");
@@ -509,6 +511,8 @@ extern "C" int gf2_pluq_solve_left_dev(gf2_dmat const *A, int rank, const int *P
     if (P[i] < 0 || P[i] >= m) return gf2_fail_msg("gf2_pluq_solve_left_dev: P[i] out of range");
   for (int j = 0; j < n; ++j)
     if (Q[j] < 0 || Q[j] >= n) return gf2_fail_msg("gf2_pluq_solve_left_dev: Q[j] out of range");
+  if (int rc = gf2_refuse_overlap(fn, "B", B, "A", A)) return rc;  // B is rewritten step by step while A is still read
+  if (gf2_device_count() <= 0) return gf2_bad_arg(fn, "no usable HIP device");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int bw = words_of(kb);
   const u64 bmask = last_mask(kb);

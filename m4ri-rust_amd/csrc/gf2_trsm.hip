@@ -228,14 +228,14 @@ std::mutex g_trsm_mu;
 }  // namespace
 
 extern "C" int gf2_trsm_dev(gf2_dmat const *T, gf2_dmat *B, int upper, int right, void *stream) {
-  if (gf2_device_count() <= 0) return gf2_fail_msg("gf2_trsm_dev: no usable HIP device");
-  if (!T || !B) return gf2_fail_msg("gf2_trsm_dev: null argument");
-  if (T->nrows != T->ncols) return gf2_fail_msg("gf2_trsm_dev: T is not square");
-  if ((right ? B->ncols : B->nrows) != T->nrows) return gf2_fail_msg("gf2_trsm_dev: dimension mismatch");
+  static const char fn[] = "gf2_trsm_dev";
+  if (gf2_check_mat(fn, "T", T) || gf2_check_mat(fn, "B", B)) return -1;
+  if (T->nrows != T->ncols) return gf2_bad_arg(fn, "T is not square");
+  if ((right ? B->ncols : B->nrows) != T->nrows) return gf2_bad_arg(fn, "dimension mismatch");
   const int n = T->nrows;
   if (n == 0 || B->nrows == 0 || B->ncols == 0) return 0;
-  if (!T->data || !B->data) return gf2_fail_msg("gf2_trsm_dev: null argument");
-  if (T->ld < words_of(n) || B->ld < words_of(B->ncols)) return gf2_fail_msg("gf2_trsm_dev: row stride smaller than row width");
+  if (int rc = gf2_refuse_overlap(fn, "B", B, "T", T)) return rc;  // blocks of B are rewritten while later steps still read T
+  if (gf2_device_count() <= 0) return gf2_bad_arg(fn, "no usable HIP device");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int d = trsm_block(n), nb = (n + d - 1) / d;
   TrsmCtx c{*T, *B, n, d, upper != 0, right != 0, nullptr, even_ld(d >> 6), nullptr, 0, s};

@@ -403,13 +403,23 @@ static int mul_naive_dev(gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B, int 
   return sync_if(sync_free, s);
 }
 
-static int check_mul_dims(const gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B) {
-  if (!C || !A || !B || !C->data || !A->data || !B->data) return gf2_fail_msg("gf2_mul_dev: null operand");
-  if (A->ncols != B->nrows || C->nrows != A->nrows || C->ncols != B->ncols)
-    return gf2_fail_msg("gf2_mul_dev: dimension mismatch");
-  if (A->ld < words_of(A->ncols) || B->ld < words_of(B->ncols) || C->ld < words_of(C->ncols))
-    return gf2_fail_msg("gf2_mul_dev: row stride smaller than row width");
+// The argument and aliasing rules of gf2_mul_dev and gf2_mul_nt_dev (include/m4ri_hip.h), checked before a device is required.  A is
+// m x l; B is l x n (nt: n x l); C is m x n.  A and B are only read and may be one matrix or overlap; C is written while other
+// workgroups still read rows of A and B, so it may share no word with either.  0: go ahead; 1: C is empty, nothing to do; -1: refused
+static int check_mul(const char *fn, const char *bname, const gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B, bool nt) {
+  if (gf2_check_mat(fn, "C", C) || gf2_check_mat(fn, "A", A) || gf2_check_mat(fn, bname, B)) return -1;
+  if (A->ncols != (nt ? B->ncols : B->nrows) || C->nrows != A->nrows || C->ncols != (nt ? B->nrows : B->ncols))
+    return gf2_bad_arg(fn, "dimension mismatch");
+  if (C->nrows == 0 || C->ncols == 0) return 1;
+  if (gf2_refuse_overlap(fn, "C", C, "A", A) || gf2_refuse_overlap(fn, "C", C, bname, B)) return -1;
   return 0;
+}
+
+// an inner dimension of 0: the product is the zero matrix
+static int mul_of_nothing(const char *fn, gf2_dmat *C, int accumulate, hipStream_t s) {
+  if (accumulate) return 0;
+  const hipError_t e = gf2k_xor2d(C->data, C->ld, nullptr, 0, nullptr, 0, C->nrows, words_of(C->ncols), s);
+  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
 }
 
 int gf2_mul_dispatch(gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B, int accumulate, int algo, int param, hipStream_t s, bool sync_free) {
@@ -444,19 +454,21 @@ int gf2_mul_dispatch(gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B, int accu
 
 extern "C" int gf2_mul_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *B, int accumulate, int algo, int param,
                            void *stream) {
+  static const char fn[] = "gf2_mul_dev";
+  if (int rc = check_mul(fn, "B", C, A, B, false)) return rc < 0 ? rc : 0;
   if (int rc = gf2_require_device()) return rc;
-  if (int rc = check_mul_dims(C, A, B)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (A->ncols == 0) return mul_of_nothing(fn, C, accumulate, s);
   return gf2_mul_dispatch(C, A, B, accumulate, algo, param, s, /*sync_free=*/false);
 }
 
 extern "C" int gf2_mul_nt_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *Bt, int accumulate, void *stream) {
+  static const char fn[] = "gf2_mul_nt_dev";
+  if (int rc = check_mul(fn, "Bt", C, A, Bt, true)) return rc < 0 ? rc : 0;
   if (int rc = gf2_require_device()) return rc;
-  if (!C || !A || !Bt || !C->data || !A->data || !Bt->data) return gf2_fail_msg("gf2_mul_nt_dev: null operand");
-  if (A->ncols != Bt->ncols || C->nrows != A->nrows || C->ncols != Bt->nrows)
-    return gf2_fail_msg("gf2_mul_nt_dev: dimension mismatch");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int m = A->nrows, l = A->ncols, n = Bt->nrows;
+  if (l == 0) return mul_of_nothing(fn, C, accumulate, s);
   if (widevec_shape(m, l, n)) {  // long rows, at most 64 vectors: a wave per row (Bt is already what that kernel reads)
     HIP_TRY(gf2k_widevec(A->data, A->ld, Bt->data, Bt->ld, C->data, C->ld, m, l, n < 32 ? n : 32, accumulate, 0, s));
     if (n > 32) HIP_TRY(gf2k_widevec(A->data, A->ld, Bt->data + 32 * Bt->ld, Bt->ld, C->data, C->ld, m, l, n - 32, 1, 32, s));
@@ -475,29 +487,48 @@ extern "C" int gf2_strassen_levels(int m, int l, int n, int algo, int param) {
   return L;
 }
 
+// C = A xor B.  Every word is read and written by the one thread that owns it, so C may be A, B or both (mzd_add(A, A, B), the
+// reference's +=); any other overlap of C with an operand would read words another thread has already replaced.
 extern "C" int gf2_add_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *B, void *stream) {
-  if (int rc = gf2_require_device()) return rc;
+  static const char fn[] = "gf2_add_dev";
+  if (gf2_check_mat(fn, "C", C) || gf2_check_mat(fn, "A", A) || gf2_check_mat(fn, "B", B)) return -1;
   if (A->nrows != B->nrows || A->ncols != B->ncols || C->nrows != A->nrows || C->ncols != A->ncols)
-    return gf2_fail_msg("gf2_add_dev: dimension mismatch");
+    return gf2_bad_arg(fn, "dimension mismatch");
+  if (C->nrows == 0 || C->ncols == 0) return 0;
+  if (!gf2_same_view(C, A) && gf2_refuse_overlap(fn, "C", C, "A", A)) return -1;
+  if (!gf2_same_view(C, B) && gf2_refuse_overlap(fn, "C", C, "B", B)) return -1;
+  if (int rc = gf2_require_device()) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   HIP_TRY(gf2k_xor2d(C->data, C->ld, A->data, A->ld, B->data, B->ld, A->nrows, words_of(A->ncols), s));
   return 0;
 }
 
 extern "C" int gf2_transpose_dev(gf2_dmat *D, gf2_dmat const *S, void *stream) {
+  static const char fn[] = "gf2_transpose_dev";
+  if (gf2_check_mat(fn, "D", D) || gf2_check_mat(fn, "S", S)) return -1;
+  if (D->nrows != S->ncols || D->ncols != S->nrows) return gf2_bad_arg(fn, "dimension mismatch");
+  if (S->nrows == 0 || S->ncols == 0) return 0;
+  if (gf2_refuse_overlap(fn, "D", D, "S", S)) return -1;
   if (int rc = gf2_require_device()) return rc;
-  if (D->nrows != S->ncols || D->ncols != S->nrows) return gf2_fail_msg("gf2_transpose_dev: dimension mismatch");
   hipStream_t s = static_cast<hipStream_t>(stream);
   HIP_TRY(gf2k_transpose(D->data, D->ld, S->data, S->ld, S->nrows, S->ncols, s));
   return 0;
 }
 
+// both matrices are only read: they may be one matrix or overlap in any way
 extern "C" int gf2_equal_dev(gf2_dmat const *A, gf2_dmat const *B, int *equal, void *stream) {
-  if (int rc = gf2_require_device()) return rc;
+  static const char fn[] = "gf2_equal_dev";
+  if (gf2_check_mat(fn, "A", A) || gf2_check_mat(fn, "B", B)) return -1;
+  if (!equal) return gf2_bad_arg(fn, "equal is null");
   if (A->nrows != B->nrows || A->ncols != B->ncols) {
     *equal = 0;
     return 0;
   }
+  if (A->nrows == 0 || A->ncols == 0) {
+    *equal = 1;
+    return 0;
+  }
+  if (int rc = gf2_require_device()) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   void *flag = nullptr;
   if (int rc = gf2_dev_alloc(&flag, sizeof(int))) return rc;

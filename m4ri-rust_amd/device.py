@@ -145,7 +145,9 @@ class DMat:
 
 
 def mul(A, B, C=None, accumulate=False, algo="auto", param=0, stream=None):
-    """C (+)= A*B on the device; asynchronous on `stream` (int hipStream_t or None)."""
+    """C (+)= A*B on the device; asynchronous on `stream` (int hipStream_t or None).
+    Aliasing: A and B are only read -- mul(A, A) squares, and the two may overlap; C may share no word with A or B, with or without
+    `accumulate` (HipError, "overlap").  C, A and B may be three disjoint column ranges of one parent."""
     if C is None:
         C = DMat(A.nrows, B.ncols)
     rc = _lib.lib().gf2_mul_dev(C._on(stream), A._on(stream), B._on(stream), int(accumulate), ALGOS[algo], param, stream)
@@ -154,6 +156,7 @@ def mul(A, B, C=None, accumulate=False, algo="auto", param=0, stream=None):
 
 
 def mul_nt(A, Bt, C=None, accumulate=False, stream=None):
+    """C (+)= A * Bt^T.  Aliasing as mul(): mul_nt(A, A) is the Gram matrix A A^T; C may share no word with A or Bt."""
     if C is None:
         C = DMat(A.nrows, Bt.nrows)
     _lib.check(_lib.lib().gf2_mul_nt_dev(C._on(stream), A._on(stream), Bt._on(stream), int(accumulate), stream), "gf2_mul_nt_dev")
@@ -161,6 +164,8 @@ def mul_nt(A, Bt, C=None, accumulate=False, stream=None):
 
 
 def add(A, B, C=None, stream=None):
+    """C = A xor B.  Aliasing: C may be A, B or both -- add(A, B, C=A) is A += B in place (mzd_add(A, A, B)) -- and A may be B (zero); a C
+    that overlaps an operand in any other way (another row, word or ld of the same buffer) raises HipError ("overlap")."""
     if C is None:
         C = DMat(A.nrows, A.ncols)
     _lib.check(_lib.lib().gf2_add_dev(C._on(stream), A._on(stream), B._on(stream), stream), "gf2_add_dev")
@@ -168,6 +173,8 @@ def add(A, B, C=None, stream=None):
 
 
 def transpose(S, D=None, stream=None):
+    """D = S^T.  Aliasing: D may share no word with S (no in-place transposition, not for a square matrix either: HipError, "overlap");
+    D and S may be disjoint column ranges of one parent."""
     if D is None:
         D = DMat(S.ncols, S.nrows)
     _lib.check(_lib.lib().gf2_transpose_dev(D._on(stream), S._on(stream), stream), "gf2_transpose_dev")
@@ -223,7 +230,8 @@ def echelonize(A, full=True, ncols_limit=0, stream=None):
 
 
 def inverse(A, stream=None):
-    """A^-1 as a new DMat, or None if A is singular."""
+    """A^-1 as a new DMat, or None if A is singular.  (The C entry gf2_inverse_dev also inverts in place: its Ainv may be A, or overlap
+    it in any way, because A is copied into scratch before Ainv is written.)"""
     out = DMat(A.nrows, A.ncols)
     singular = ctypes.c_int(0)
     _lib.check(_lib.lib().gf2_inverse_dev(out._on(stream), A._on(stream), ctypes.byref(singular), stream),
@@ -361,7 +369,8 @@ def solve_left(A, B, check=True, stream=None):
 
 def trsm(T, B, upper=False, right=False, stream=None):
     """B = T^-1 B (right=False) or B T^-1 (right=True) in place, T unit lower (upper=False) or upper triangular: only its strict
-    triangle is read.  Asynchronous on `stream`."""
+    triangle is read.  Asynchronous on `stream`.  Aliasing: T and B may be views of one buffer, but B may share no word with T (HipError,
+    "overlap")."""
     _lib.check(_lib.lib().gf2_trsm_dev(T._on(stream), B._on(stream), int(bool(upper)), int(bool(right)), stream), "gf2_trsm_dev")
     return B
 
