@@ -1185,7 +1185,8 @@ __global__ __launch_bounds__(256) void gf2_streamk_reduce_kernel(const gf2k_mul_
   u64 v0 = (u64)a.x | ((u64)a.y << 32), v1 = (u64)a.z | ((u64)a.w << 32);
   if (wc == widthB - 1) v0 &= maskC;
   if (wc + 1 == widthB - 1) v1 &= maskC;
-  if (wc + 1 < widthB) {
+  // C is the caller's: a view may have an odd ld or start at an odd word, so the 16-byte form is taken where the address allows
+  if (wc + 1 < widthB && !(reinterpret_cast<uintptr_t>(dst) & 15)) {
     if (p.accumulate) {
       const uint4 old = *reinterpret_cast<const uint4 *>(dst);
       v0 ^= (u64)old.x | ((u64)old.y << 32);
@@ -1195,6 +1196,10 @@ __global__ __launch_bounds__(256) void gf2_streamk_reduce_kernel(const gf2k_mul_
   } else {
     if (p.accumulate) v0 ^= dst[0];
     dst[0] = v0;
+    if (wc + 1 < widthB) {
+      if (p.accumulate) v1 ^= dst[1];
+      dst[1] = v1;
+    }
   }
 }
 
@@ -1236,13 +1241,19 @@ __global__ __launch_bounds__(256) void gf2_splitk_reduce_kernel(u64 *__restrict_
     uint4 a = make_uint4(0, 0, 0, 0);
     for (int s = 0; s < ksplit; ++s) a = xor4(a, *reinterpret_cast<const uint4 *>(src + (long long)s * sP));
     u64 *dst = C + (long long)b * sC + (long long)r * ldc + w;
-    if (w + 1 < words) {
+    // C is the caller's: a view may have an odd ld or start at an odd word, so the 16-byte form is taken where the address allows
+    if (w + 1 < words && !(reinterpret_cast<uintptr_t>(dst) & 15)) {
       if (accumulate) a = xor4(a, *reinterpret_cast<const uint4 *>(dst));
       *reinterpret_cast<uint4 *>(dst) = a;
     } else {
       u64 v = (u64)a.x | ((u64)a.y << 32);
       if (accumulate) v ^= dst[0];
       dst[0] = v;
+      if (w + 1 < words) {
+        u64 v1 = (u64)a.z | ((u64)a.w << 32);
+        if (accumulate) v1 ^= dst[1];
+        dst[1] = v1;
+      }
     }
   }
 }

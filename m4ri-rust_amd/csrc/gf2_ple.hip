@@ -181,9 +181,9 @@ __global__ void __launch_bounds__(256) ple_compress_extract(const u64 *A, long l
   if (b0 < wi) {
     const u64 *row = A + (long long)i * lda;
     const int bit = sbit + b0, w = bit >> 6, sh = bit & 63;
-    v = row[w] >> sh;
-    if (sh) v |= row[w + 1] << (64 - sh);  // sbit + wi <= the node's right edge, inside the row
     const int n = wi - b0;
+    v = row[w] >> sh;
+    if (sh && sh + n > 64) v |= row[w + 1] << (64 - sh);  // only when wanted bits lie in it: word w may be the row's last
     if (n < 64) v &= (1ull << n) - 1;
   }
   S[(long long)i * sw + q] = v;

@@ -611,7 +611,10 @@ extern "C" void mzd_make_table(mzd_t const *M, rci_t r, rci_t c, int k, mzd_t *T
     gf2_die("mzd_make_table: bad arguments");
   gf2_cache_forget(T);
   const wi_t w0 = c / m4ri_radix, w = M->width;
-  for (wi_t j = w0; j < w; ++j) T->rows[0][j] = 0;
+  // T may be a window: bits of its last word past its columns are its parent's and stay
+  const word tmask = (w == T->width) ? T->high_bitmask : m4ri_ffff;
+  for (wi_t j = w0; j + 1 < w; ++j) T->rows[0][j] = 0;
+  if (w > w0) T->rows[0][w - 1] &= ~tmask;
   L[0] = 0;
   unsigned combo = 0;  // the k-bit value whose combination the current row holds
   for (unsigned i = 1; i < (1u << k); ++i) {
@@ -620,7 +623,7 @@ extern "C" void mzd_make_table(mzd_t const *M, rci_t r, rci_t c, int k, mzd_t *T
     const word *src = M->rows[r + flip], *prev = T->rows[i - 1];
     word *dst = T->rows[i];
     for (wi_t j = w0; j + 1 < w; ++j) dst[j] = prev[j] ^ src[j];
-    if (w > w0) dst[w - 1] = prev[w - 1] ^ (src[w - 1] & M->high_bitmask);
+    if (w > w0) dst[w - 1] = (dst[w - 1] & ~tmask) | ((prev[w - 1] ^ (src[w - 1] & M->high_bitmask)) & tmask);
     L[combo] = (rci_t)i;
   }
 }

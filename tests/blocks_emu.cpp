@@ -1,35 +1,9 @@
 // blocks_emu.cpp -- runs the block-copy kernel of m4ri-rust_amd/csrc/gf2_blocks.hip thread by thread on the CPU (tests/test_blocks_kernel_cpu.py
 // builds this file with the host compiler and its address / undefined-behaviour sanitizers).  The kernel text is included as it is, behind
-// stand-ins for the few HIP names it uses.  Every buffer ends with the last word of the rectangle's last row, so an access to a word that
+// the stand-ins of tests/kernel_emu.h for the few HIP names it uses.  Every buffer ends with the last word of the rectangle's last row, so an access to a word that
 // holds no bit of the rectangle -- which a GPU test could only show by faulting -- is an error report here.  Results are compared bit by bit
 // over the whole destination buffer.  KERNEL_BODY: the .hip file without its #include lines.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-#include <random>
-struct alignas(16) uint4 { uint32_t x, y, z, w; };
-static inline uint4 make_uint4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return uint4{a, b, c, d}; }
-struct dim3 { unsigned x, y, z; dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {} };
-static dim3 blockIdx, threadIdx, gridDim, blockDim;
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(x)
-typedef int hipError_t;
-typedef void *hipStream_t;
-#define hipSuccess 0
-#define hipGetLastError() 0
-static long g_threads = 0;
-#define hipLaunchKernelGGL(k, grid, block, shm, stream, ...)                                  \
-  do {                                                                                         \
-    gridDim = grid; blockDim = block;                                                          \
-    if (blockDim.x * blockDim.y != 256) { printf("bad block\n"); abort(); }                    \
-    for (unsigned bx = 0; bx < gridDim.x; ++bx) for (unsigned by = 0; by < gridDim.y; ++by)    \
-      for (unsigned ty = 0; ty < blockDim.y; ++ty) for (unsigned tx = 0; tx < blockDim.x; ++tx) { \
-        blockIdx = dim3(bx, by); threadIdx = dim3(tx, ty); ++g_threads; k(__VA_ARGS__); }      \
-  } while (0)
+#include "kernel_emu.h"
 #include KERNEL_BODY
 
 static int getbit(const u64 *p, long long ld, long long r, long long c) { return (p[r * ld + (c >> 6)] >> (c & 63)) & 1; }
