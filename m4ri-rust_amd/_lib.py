@@ -179,6 +179,15 @@ _PROTOS = {
 # ctypes but are not part of the header check's mzd_* / gf2_* pattern)
 DECLARED_SYMBOLS = tuple(k for k in _PROTOS if not k.lower().startswith("mzp_"))
 
+# what the companion header include/m4ri_hip_gather.h declares: a table of its own, so that DECLARED_SYMBOLS stays the list of
+# m4ri_hip.h (tests/test_gather_contract.py checks this header against the library)
+_GATHER_PROTOS = {
+    "gf2_gather_rows_dev": (_I, [DMatP, DMatP, ctypes.c_void_p, _I, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_gather_cols_dev": (_I, [DMatP, DMatP, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_gather_cols_plan": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
+}
+GATHER_SYMBOLS = tuple(_GATHER_PROTOS)
+
 _lib = None
 
 
@@ -191,7 +200,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C m4ri-rust_amd/csrc`). There is no fallback for the HIP multiply path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in _PROTOS.items():
+        for name, (res, args) in list(_PROTOS.items()) + list(_GATHER_PROTOS.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -139,6 +139,14 @@ class DMat:
         """Rows [start_row, high_row) x columns [start_col, high_col) as a new DMat."""
         return submatrix(self, start_row, start_col, high_row, high_col)
 
+    def take_rows(self, idx):
+        """The rows idx[0], idx[1], ... of self as a new DMat (numpy's self[idx]; -1: a zero row; duplicates allowed)."""
+        return gather_rows(self, idx)[0]
+
+    def take_cols(self, idx):
+        """The columns idx[0], idx[1], ... of self as a new DMat (numpy's self[:, idx]; -1: a zero column; duplicates allowed)."""
+        return gather_cols(self, idx)[0]
+
     def set_window(self, start_row, start_col, other):
         """Overwrite the block of other's shape at (start_row, start_col) with other."""
         copy_block(self, start_row, start_col, other, 0, 0, other.nrows, other.ncols)
@@ -304,6 +312,81 @@ def inverse_batch(A, n, Ainv=None, singular=None, stream=None):
     if singular is not None:
         return Ainv, None
     return Ainv, own.read(stream) if own else np.zeros(0, dtype=np.int32)
+
+
+class _IntUpload(_IntScratch):
+    """host ints as a device array, through device words like _IntScratch: 128 ints per row of a dense DMat"""
+
+    def __init__(self, values, stream=None):
+        v = np.ascontiguousarray(np.asarray(values).reshape(-1), dtype=np.int32)
+        self.count = len(v)
+        rows = max((self.count + 127) // 128, 1)
+        full = np.zeros(rows * 128, dtype=np.int32)
+        full[:self.count] = v
+        self.mat = DMat.from_words(full.view(np.uint64).reshape(rows, 64), 4096, stream)
+
+
+def _device_ints(idx, count, what, stream):
+    """idx as (address, owner): an int is a raw device address and only passed on; a list or numpy int array is uploaded"""
+    if isinstance(idx, (int, np.integer)):
+        return int(idx), None
+    arr = np.asarray(idx)
+    if arr.size != count:
+        raise ValueError("%s: idx holds %d indices, D needs %d" % (what, arr.size, count))
+    if count == 0:
+        return None, None
+    if arr.dtype.kind not in "iu" or arr.min() < -(1 << 31) or arr.max() >= (1 << 31):
+        raise ValueError("%s: idx must hold int32 values" % what)
+    up = _IntUpload(arr, stream)
+    return up.ptr, up
+
+
+def _gather(name, D, S, ptr, accumulate, bad, stream):
+    own = None
+    if bad is None:
+        own = _IntUpload([0], stream)
+        bad = own.ptr
+    L = _lib.lib()
+    if name == "gf2_gather_rows_dev":
+        rc = L.gf2_gather_rows_dev(D._on(stream), S._on(stream), ptr, int(bool(accumulate)), bad or None, stream)
+    else:
+        rc = L.gf2_gather_cols_dev(D._on(stream), S._on(stream), ptr, bad or None, stream)
+    _lib.check(rc, name)
+    return D, (bool(own.read(stream)[0]) if own else None)
+
+
+def gather_rows(S, idx, D=None, accumulate=False, bad=SKIP, stream=None):
+    """D[i] (^)= S[idx[i]] for every row i of D (default: a new len(idx) x S.ncols matrix) -> (D, bad).  An index of -1 gives a zero row
+    (accumulate: leaves the row), any other value outside S's rows likewise and is reported in `bad`.  `idx` is a raw device address of
+    D.nrows int32 (e.g. a torch int32 tensor's data_ptr()) or a list / numpy int array that the wrapper uploads.  `bad` follows
+    `singular` of inverse_batch(): a raw device address of an int the caller has zeroed, or SKIP (0) -- the call then only enqueues on
+    `stream` and None is returned in its place -- or None: the wrapper allocates a zeroed int, WAITS for `stream` and returns a bool.
+    Duplicates are fine; D may share no word with S (HipError, "overlap")."""
+    if D is None:
+        if isinstance(idx, (int, np.integer)):
+            raise ValueError("gather_rows: a raw idx address needs D (its row count is the number of indices)")
+        D = DMat(int(np.asarray(idx).size), S.ncols)
+    ptr, keep = _device_ints(idx, D.nrows, "gather_rows", stream)
+    return _gather("gf2_gather_rows_dev", D, S, ptr, accumulate, bad, stream)
+
+
+def gather_cols(S, idx, D=None, bad=SKIP, stream=None):
+    """D[r][j] = S[r][idx[j]] for every column j of D (default: a new S.nrows x len(idx) matrix) -> (D, bad); idx and bad as in
+    gather_rows(), -1 gives a zero column.  gather_cols_plan() tells which kernel a shape runs on."""
+    if D is None:
+        if isinstance(idx, (int, np.integer)):
+            raise ValueError("gather_cols: a raw idx address needs D (its column count is the number of indices)")
+        D = DMat(S.nrows, int(np.asarray(idx).size))
+    ptr, keep = _device_ints(idx, D.ncols, "gather_cols", stream)
+    return _gather("gf2_gather_cols_dev", D, S, ptr, False, bad, stream)
+
+
+def gather_cols_plan(nrows, s_ncols, d_ncols):
+    """Which path a column gather of this shape takes (no device needed) -> (path, threads per workgroup, LDS bytes per workgroup, rows
+    per workgroup, scratch bytes) with path 0 = the fused LDS kernel, 1 = transpose / row gather / transpose; None for a bad shape."""
+    out = (ctypes.c_longlong * 4)()
+    path = _lib.lib().gf2_gather_cols_plan(nrows, s_ncols, d_ncols, out)
+    return None if path < 0 else (path, out[0], out[1], out[2], out[3])
 
 
 def nullspace(A, stream=None):
