@@ -188,6 +188,16 @@ _GATHER_PROTOS = {
 }
 GATHER_SYMBOLS = tuple(_GATHER_PROTOS)
 
+# ... and include/m4ri_hip_weight.h (tests/test_weight_contract.py)
+_WEIGHT_PROTOS = {
+    "gf2_row_weights_dev": (_I, [DMatP, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_col_weights_dev": (_I, [DMatP, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_count_ones_dev": (_I, [DMatP, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_select_weights_dev": (_I, [ctypes.c_void_p, _I, _I, _I, ctypes.c_void_p, _I, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_weights_plan": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
+}
+WEIGHT_SYMBOLS = tuple(_WEIGHT_PROTOS)
+
 _lib = None
 
 
@@ -200,7 +210,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C m4ri-rust_amd/csrc`). There is no fallback for the HIP multiply path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in list(_PROTOS.items()) + list(_GATHER_PROTOS.items()):
+        for name, (res, args) in list(_PROTOS.items()) + list(_GATHER_PROTOS.items()) + list(_WEIGHT_PROTOS.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

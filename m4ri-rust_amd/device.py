@@ -147,6 +147,20 @@ class DMat:
         """The columns idx[0], idx[1], ... of self as a new DMat (numpy's self[:, idx]; -1: a zero column; duplicates allowed)."""
         return gather_cols(self, idx)[0]
 
+    # -- Hamming weights on the device (include/m4ri_hip_weight.h) --
+    def row_weights(self):
+        """The Hamming weight of every row as a numpy int32 array."""
+        return row_weights(self)
+
+    def col_weights(self):
+        """The number of set bits of every column as a numpy int32 array."""
+        return col_weights(self)
+
+    def count_ones(self):
+        """The number of set bits.  On a vector (one row or one column) this is the reference's BinVector / BinMatrix count_ones
+        (binary_matrix.rs:172-189, binary_vector.rs:112); on a matrix it is the total over all rows, where the reference panics."""
+        return count_ones(self)
+
     def set_window(self, start_row, start_col, other):
         """Overwrite the block of other's shape at (start_row, start_col) with other."""
         copy_block(self, start_row, start_col, other, 0, 0, other.nrows, other.ncols)
@@ -387,6 +401,72 @@ def gather_cols_plan(nrows, s_ncols, d_ncols):
     out = (ctypes.c_longlong * 4)()
     path = _lib.lib().gf2_gather_cols_plan(nrows, s_ncols, d_ncols, out)
     return None if path < 0 else (path, out[0], out[1], out[2], out[3])
+
+
+_WEIGHT_WHAT = {"rows": 0, "cols": 1, "columns": 1, "total": 2}
+
+
+def weights_plan(what, nrows, ncols):
+    """Which kernel the weights of an nrows x ncols matrix run on (no device needed); what: "rows", "cols" or "total" (0, 1, 2)
+    -> (variant id, threads per workgroup, rows per workgroup and pass, rows a lane takes before it empties its bit-sliced counters
+    (columns; else 0), scratch bytes); None for a bad shape.  The variant ids are listed in include/m4ri_hip_weight.h."""
+    out = (ctypes.c_longlong * 4)()
+    v = _lib.lib().gf2_weights_plan(_WEIGHT_WHAT.get(what, what), nrows, ncols, out)
+    return None if v < 0 else (v, out[0], out[1], out[2], out[3])
+
+
+def _weights(name, A, count, out, stream):
+    own = _IntScratch(count) if out is None and count > 0 else None
+    rc = getattr(_lib.lib(), name)(A._on(stream), own.ptr if own else out, stream)
+    _lib.check(rc, name)
+    if out is not None:
+        return None
+    return own.read(stream) if own else np.zeros(0, dtype=np.int32)
+
+
+def row_weights(A, out=None, stream=None):
+    """The Hamming weight of every row of A.  `out` is a raw device address of A.nrows int32 (e.g. a torch int32 tensor's data_ptr()):
+    the call only enqueues on `stream` and None is returned; or None: the wrapper allocates scratch, WAITS for `stream` and returns a
+    numpy int32 array.  Only A's ncols bits count; the array is overwritten, the caller zeroes nothing."""
+    return _weights("gf2_row_weights_dev", A, A.nrows, out, stream)
+
+
+def col_weights(A, out=None, stream=None):
+    """The number of rows of A with bit j set, for every column j (A.ncols int32); `out` as in row_weights().  weights_plan("cols", ...)
+    tells how the rows are cut into bands."""
+    return _weights("gf2_col_weights_dev", A, A.ncols, out, stream)
+
+
+def count_ones(A, stream=None):
+    """The number of set bits of A as a Python int (nrows * ncols can pass 2^32); WAITS for `stream`."""
+    own = _IntScratch(2)
+    _lib.check(_lib.lib().gf2_count_ones_dev(A._on(stream), own.ptr, stream), "gf2_count_ones_dev")
+    return int(own.read(stream).view(np.uint64)[0])
+
+
+def select_weights(weights, n, lo, hi, idx=None, cap=None, count=None, stream=None):
+    """The indices i < n with lo <= weights[i] <= hi, ascending -> (idx, count).  `weights` is a raw device address of n int32 (what
+    row_weights / col_weights wrote) or a list / numpy int array that the wrapper uploads.  At most `cap` (default: n) indices are
+    stored; `count` is how many there are in all and may exceed cap.  Each of `idx` (cap int32) and `count` (one int32) is a raw device
+    address -- the kernel writes there, None is returned in its place -- or None: the wrapper allocates scratch, WAITS for `stream`
+    and returns numpy (idx cut to min(count, cap) when the wrapper owns the count too) / an int.  idx=SKIP (0) is a count-only call.
+    The device array idx feeds gather_rows / gather_cols as it is."""
+    if cap is None:
+        cap = n
+    if idx is not None and idx == SKIP:
+        cap = 0
+    wptr, keep = _device_ints(weights, n, "select_weights", stream)
+    own_i = _IntScratch(cap) if idx is None and cap > 0 else None
+    own_c = _IntScratch(1) if count is None else None
+    rc = _lib.lib().gf2_select_weights_dev(wptr, n, lo, hi, own_i.ptr if own_i else (idx or None), cap, own_c.ptr if own_c else count, stream)
+    _lib.check(rc, "gf2_select_weights_dev")
+    out_c = int(own_c.read(stream)[0]) if own_c and (n > 0 or cap > 0) else (0 if own_c else None)
+    out_i = None
+    if idx is None:
+        out_i = own_i.read(stream) if own_i else np.zeros(0, dtype=np.int32)
+        if out_c is not None:
+            out_i = out_i[:min(out_c, cap)]
+    return out_i, out_c
 
 
 def nullspace(A, stream=None):
