@@ -198,6 +198,16 @@ _WEIGHT_PROTOS = {
 }
 WEIGHT_SYMBOLS = tuple(_WEIGHT_PROTOS)
 
+# ... and include/m4ri_hip_wht.h (tests/test_wht_contract.py)
+_WHT_PROTOS = {
+    "gf2_lpn_tally_dev": (_I, [DMatP, _I, _I, _I, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_wht_dev": (_I, [ctypes.c_void_p, _I, ctypes.c_void_p]),
+    "gf2_lpn_errors_dev": (_I, [DMatP, _I, _I, _I, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_min_weight_dev": (_I, [ctypes.c_void_p, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_wht_plan": (_I, [_I, ctypes.POINTER(ctypes.c_longlong)]),
+}
+WHT_SYMBOLS = tuple(_WHT_PROTOS)
+
 _lib = None
 
 
@@ -210,7 +220,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C m4ri-rust_amd/csrc`). There is no fallback for the HIP multiply path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in list(_PROTOS.items()) + list(_GATHER_PROTOS.items()) + list(_WEIGHT_PROTOS.items()):
+        for name, (res, args) in list(_PROTOS.items()) + list(_GATHER_PROTOS.items()) + list(_WEIGHT_PROTOS.items()) + list(_WHT_PROTOS.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

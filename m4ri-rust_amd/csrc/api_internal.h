@@ -97,7 +97,8 @@ inline int gf2_refuse_overlap(const char *fn, const char *w, gf2_dmat const *W, 
 // scratch from the per-stream arena (grown on demand, reused by later calls on the stream, released by gf2_trim).  Slot 0: Strassen
 // operand arena / transposed operand of the naive entry; 1: split-K and stream-K partial tiles; 2: packed A; 3: the copies of a padded
 // product; 4 / 5: gf2_trsm.hip (block inverses / a leaf's result); 6 / 7: gather/gather_host.cpp (S^T / the gathered rows of the composed
-// column gather); 8 / 9: weight/weight_host.cpp (per-band column sums / block counts of the selection)
+// column gather); 8 / 9: weight/weight_host.cpp (per-band column sums / block counts of the selection); 10: wht/wht_host.cpp (the
+// per-workgroup minima of gf2_min_weight_dev)
 int gf2_stream_scratch(hipStream_t s, size_t bytes, void **out, int slot = 0);
 // counts a run of a host routine of the size dispatch (gf2_host_small_calls)
 void gf2_note_host_small_call();

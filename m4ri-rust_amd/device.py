@@ -161,6 +161,11 @@ class DMat:
         (binary_matrix.rs:172-189, binary_vector.rs:112); on a matrix it is the total over all rows, where the reference panics."""
         return count_ones(self)
 
+    def lpn_errors(self, c0, k, label_col):
+        """For every secret s < 2^k the number of rows whose bits [c0, c0 + k) disagree with bit label_col under s (numpy int32[2^k]):
+        tally, Walsh-Hadamard transform, (N - F) / 2 on the device (include/m4ri_hip_wht.h)."""
+        return lpn_errors(self, c0, k, label_col)
+
     def set_window(self, start_row, start_col, other):
         """Overwrite the block of other's shape at (start_row, start_col) with other."""
         copy_block(self, start_row, start_col, other, 0, 0, other.nrows, other.ncols)
@@ -467,6 +472,61 @@ def select_weights(weights, n, lo, hi, idx=None, cap=None, count=None, stream=No
         if out_c is not None:
             out_i = out_i[:min(out_c, cap)]
     return out_i, out_c
+
+
+def wht_plan(k):
+    """How a Walsh-Hadamard transform of 2^k int32 runs (no device needed) -> (passes, first level of every pass + [k], threads per
+    workgroup, LDS bytes, tally variant (0: histogram in LDS, 1: global atomics), scratch bytes of min_weight for n = 2^k); None for a
+    k outside 0 .. 30.  Pass p covers the levels [first[p], first[p + 1])."""
+    out = (ctypes.c_longlong * 12)()
+    passes = _lib.lib().gf2_wht_plan(k, out)
+    return None if passes < 0 else (passes, [int(out[p]) for p in range(passes)] + [k], out[8], out[9], out[10], out[11])
+
+
+def _wht_array(name, call, count, out, stream):
+    own = _IntScratch(count) if out is None else None
+    _lib.check(call(own.ptr if own else out), name)
+    return own.read(stream) if own else None
+
+
+def lpn_tally(P, c0, k, label_col=-1, out=None, stream=None):
+    """f[v] = (rows of P whose bits [c0, c0 + k) read v and whose bit label_col is 0) - (... is 1), v < 2^k; label_col = -1: the plain
+    histogram.  `out` is a raw device address of 2^k int32 (e.g. a torch int32 tensor's data_ptr()): the call only enqueues on `stream`
+    and None is returned; or None: the wrapper allocates scratch, WAITS for `stream` and returns a numpy int32 array."""
+    L = _lib.lib()
+    return _wht_array("gf2_lpn_tally_dev", lambda p: L.gf2_lpn_tally_dev(P._on(stream), c0, k, label_col, p, stream), 1 << k, out, stream)
+
+
+def wht(f, k, stream=None):
+    """The Walsh-Hadamard transform of 2^k int32, modulo 2^32.  `f` is a raw device address (16-byte aligned when k >= 2): transformed in
+    place, the call only enqueues on `stream` and None is returned; or a list / numpy int array that the wrapper uploads: it WAITS for
+    `stream` and returns a numpy int32 array."""
+    if isinstance(f, (int, np.integer)):
+        _lib.check(_lib.lib().gf2_wht_dev(int(f), k, stream), "gf2_wht_dev")
+        return None
+    ptr, keep = _device_ints(f, 1 << k, "wht", stream)
+    _lib.check(_lib.lib().gf2_wht_dev(ptr, k, stream), "gf2_wht_dev")
+    return keep.read(stream)
+
+
+def lpn_errors(P, c0, k, label_col, out=None, stream=None):
+    """errors[s] = the rows i of P with <P[i][c0 .. c0 + k), s> != P[i][label_col], for every s < 2^k: what col_weights(P * [S ; 1])
+    gives for S = all 2^k vectors.  `out` as in lpn_tally() (16-byte aligned when k >= 2); the array feeds select_weights / min_weight
+    as it is."""
+    L = _lib.lib()
+    return _wht_array("gf2_lpn_errors_dev", lambda p: L.gf2_lpn_errors_dev(P._on(stream), c0, k, label_col, p, stream), 1 << k, out, stream)
+
+
+def min_weight(w, n, idx=None, val=None, stream=None):
+    """The smallest of w[0 .. n) and the LOWEST index that holds it -> (idx, val).  `w` is a raw device address of n int32 or a list /
+    numpy int array that the wrapper uploads.  Each of `idx` and `val` is a raw device address of one int32 -- the kernel writes there,
+    None is returned in its place -- or None: the wrapper allocates scratch, WAITS for `stream` and returns an int."""
+    wptr, keep = _device_ints(w, n, "min_weight", stream)
+    own_i = _IntScratch(1) if idx is None else None
+    own_v = _IntScratch(1) if val is None else None
+    rc = _lib.lib().gf2_min_weight_dev(wptr, n, own_i.ptr if own_i else idx, own_v.ptr if own_v else val, stream)
+    _lib.check(rc, "gf2_min_weight_dev")
+    return (int(own_i.read(stream)[0]) if own_i else None), (int(own_v.read(stream)[0]) if own_v else None)
 
 
 def nullspace(A, stream=None):
