@@ -1,6 +1,6 @@
 // gf2_elim.hip -- row echelon forms over GF(2) on gfx950, device resident.
 //
-// Replaces the elimination entry points the friendly layer reaches (paths relative to /root/reference):
+// Replaces the elimination entry points the friendly layer reaches (files of the m4ri-rust sources):
 //   mzd_echelonize / _m4ri / _pluq   m4ri-sys/src/echelonform.rs:16-37   (BinMatrix::echelonize / rank,
 //                                                                          binary_matrix.rs:246-261)
 //   mzd_inv_m4ri                     m4ri-sys/src/brilliantrussian.rs:201-208  (BinMatrix::inverted, :263-268)

@@ -1,8 +1,8 @@
 // gf2_lpn.inc -- single-phase streaming kernels for batches of LPN-style products (BASELINE config 5):
 // C (m x n) = A (m x l) * B (l x n) with l <= 256 and n <= 256, m large.  mzd_mul_naive as `mul_slice` / `&A * &v` reach it
-// (/root/reference/m4ri-rust/src/friendly/binary_matrix.rs:416-431, /root/reference/m4ri-sys/src/mzd.rs:150-168).
-// Included by gf2_kernels.hip (the product) and by tools/lpn_lab.hip (development harness); needs u32 / u64, the lds_* typedefs,
-// xor4 and static_for.
+// (m4ri-rust's BinMatrix::mul_slice and its `*` operators).
+// Included by gf2_kernels.hip (the product: launched by gf2k_tallskinny there) and by tools/lpn_lab.hip
+// (development harness); needs u32 / u64, the lds_* typedefs, xor4 and static_for.
 //
 // Both kernels keep the Four-Russians tables of ALL 256 bits of the inner dimension resident in LDS, built once per workgroup,
 // and stream the rows of A through them: a lane owns a whole 32-byte row, looks its fields up, stores its row of C and goes on

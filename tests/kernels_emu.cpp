@@ -275,7 +275,7 @@ static long run_rowparity() {
   return cases;
 }
 
-// gf2k_packB (development builds only): dword d of rows 8 c .. 8 c + 7 of B -> the 32 bytes of lane d % 64 in block (tile d / 64, chunk
+// gf2k_packB (development builds only, tools/gf2_kernels_dev_thin.inc): dword d of rows 8 c .. 8 c + 7 of B -> the 32 bytes of lane d % 64 in block (tile d / 64, chunk
 // c); rows past l, dwords past n's last and the padding chunks are zeros.  Bp is the tool's own allocation: 16-byte aligned.
 static long run_packB() {
   long cases = 0;

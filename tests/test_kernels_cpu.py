@@ -17,6 +17,8 @@ import kernel_text
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "m4ri-rust_amd", "csrc")
 FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+# the part of gf2_kernels.hip that only development builds include (relative to CSRC, like the #include that names it)
+DEV_THIN = os.path.join("..", "..", "tools", "gf2_kernels_dev_thin.inc")
 
 # One program per group (built and run side by side: the three-level Strassen passes alone take the compiler half a minute).
 # group -> file -> what is cut out of it, in the order the program needs it: constants, structs, helpers, kernels, launchers
@@ -26,9 +28,10 @@ PIECES = {
         ("gf2_kernels.hip", [
             "xor4", "grid_for", "kTileWords7", "v8_tile", "v8_decode",
             "gf2_streamk_reduce_kernel", "gf2_packA_kernel", "gf2_splitk_reduce_kernel", "gf2_rowparity_kernel", "gf2_xor2d_kernel",
-            "gf2_padcopy_kernel", "gf2_fill_random_kernel", "gf2_packB_kernel",
-            "gf2k_packA", "gf2k_packB_chunks", "gf2k_packB", "gf2k_rowparity", "gf2k_xor2d", "gf2k_padcopy", "gf2k_fill_random",
+            "gf2_padcopy_kernel", "gf2_fill_random_kernel",
+            "gf2k_packA", "gf2k_rowparity", "gf2k_xor2d", "gf2k_padcopy", "gf2k_fill_random",
         ]),
+        (DEV_THIN, ["gf2_packB_kernel", "gf2k_packB_chunks", "gf2k_packB"]),  # development builds only
     ],
     "STRASSEN": [
         ("gf2_kernels.hip", [
@@ -122,7 +125,7 @@ RULE_WORDS = {"cross-lane", "LDS", "barriers", "atomics", "inline assembly"}
 
 
 def kernel_sources():
-    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.inc")))
+    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.inc"))) + [os.path.join(CSRC, DEV_THIN)]
 
 
 def test_every_kernel_is_classified():
@@ -140,6 +143,36 @@ def test_every_kernel_is_classified():
             assert word in RULE_WORDS, (name, word)
     cut = {n for group in PIECES.values() for _, ns in group for n in ns}
     assert not (set(EMULATED) - {"gf2_copy_block_kernel"}) - cut, "emulated, but not cut out of its file"
+
+
+def make_list(path, var):
+    """the words of `var := ...` in a makefile, continuation lines joined"""
+    with open(path) as f:
+        text = f.read().replace("\\\n", " ")
+    return re.search(r"^%s\s*:?=(.*)$" % var, text, re.M).group(1).split()
+
+
+def test_every_included_inc_is_a_dependency_of_the_build():
+    """gf2_kernels.hip includes text from other files (today gf2_lpn.inc and, in development builds, four files under tools/): an edit
+    of such a file rebuilds the library only if it is in LIB_HDR (csrc/sources.mk) or, for one under tools/, in DEV_DEPS
+    (tools/Makefile).  Whatever is cut out of gf2_kernels.hip later is held to the same rule by the walk below."""
+    root = os.path.dirname(HERE)
+    tools = os.path.join(root, "tools")
+    parts, todo = [], [os.path.join(CSRC, "gf2_kernels.hip")]
+    while todo:
+        path = todo.pop()
+        with open(path) as f:
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+\.inc)"', f.read(), re.M):
+                p = os.path.normpath(os.path.join(os.path.dirname(path), inc))
+                assert os.path.isfile(p), (path, inc)
+                if p not in parts:
+                    parts.append(p)
+                    todo.append(p)
+    lib_hdr = {os.path.normpath(os.path.join(CSRC, w)) for w in make_list(os.path.join(CSRC, "sources.mk"), "LIB_HDR")}
+    dev_deps = {os.path.normpath(os.path.join(tools, w)) for w in make_list(os.path.join(tools, "Makefile"), "DEV_DEPS") if "$" not in w}
+    assert len(parts) >= 5, parts  # gf2_lpn.inc and four files of development builds when this test was written
+    for p in parts:
+        assert p in (dev_deps if os.path.dirname(p) == tools else lib_hdr), "%s: not a dependency of the build" % os.path.relpath(p, root)
 
 
 def build_body(tmp_path, group):

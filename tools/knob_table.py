@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generates the table of every M4RI_HIP_* environment variable the library reads:
      python tools/knob_table.py > /tmp/knobs.md     (tests/test_host_abi.py checks that INTEGRATION.md lists every knob)
-A knob is a call env_int("M4RI_HIP_X", default) or getenv("M4RI_HIP_X") in m4ri-rust_amd/csrc; variables read only inside
+A knob is a call env_int("M4RI_HIP_X", default) or getenv("M4RI_HIP_X") in m4ri-rust_amd/csrc or in a part of gf2_kernels.hip under tools/; variables read only there or inside
 #ifdef GF2K_DEV_VARIANTS blocks are marked "development builds only" (tools/libm4ri_hip_dev.so)."""
 import os
 import re
@@ -40,12 +40,14 @@ DESCRIPTIONS = {
 
 def knobs():
     found = {}
-    for fn in sorted(os.listdir(SRC)):
-        if not fn.endswith((".cpp", ".hip", ".inc", ".h")):
-            continue
-        depth_dev = []  # stack of booleans: is this #if level a GF2K_DEV_VARIANTS block
+    files = [(fn, os.path.join(SRC, fn), False) for fn in sorted(os.listdir(SRC)) if fn.endswith((".cpp", ".hip", ".inc", ".h"))]
+    # the parts of gf2_kernels.hip that live under tools/: included under GF2K_DEV_VARIANTS only
+    tools = os.path.join(ROOT, "tools")
+    files += [("tools/" + fn, os.path.join(tools, fn), True) for fn in sorted(os.listdir(tools)) if fn.startswith("gf2_kernels_") and fn.endswith(".inc")]
+    for fn, path, dev_file in files:
+        depth_dev = [True] if dev_file else []  # stack of booleans: is this #if level a GF2K_DEV_VARIANTS block
         func = "file scope"
-        for ln, line in enumerate(open(os.path.join(SRC, fn)), 1):
+        for ln, line in enumerate(open(path), 1):
             st = line.strip()
             if st.startswith("#if"):
                 depth_dev.append("GF2K_DEV_VARIANTS" in st and not st.startswith("#ifndef"))
