@@ -255,7 +255,9 @@ int gf2_dmat_fill_random_block(gf2_dmat *M, uint64_t seed, int64_t row0, int64_t
  * and gf2_stack_dev state theirs in the paragraph above them; gf2_nullspace_dev allocates K itself, so K cannot alias A. */
 
 /* C (+)= A*B on `stream` (hipStream_t, NULL = default stream); asynchronous.
- * algo: GF2_ALGO_*; param: Strassen levels when algo==STRASSEN (0 = automatic), else ignored.
+ * algo: GF2_ALGO_*; param: Strassen levels when algo==STRASSEN (0 = automatic), else ignored.  An explicit level count is honoured as
+ * given (at most 6, and as far as the arena fits into device memory): M4RI_HIP_STRASSEN_MAX_LEVELS and M4RI_HIP_STRASSEN_LEAF_MIN
+ * bound the automatic choice only.
  * Aliasing: A and B are only read -- A may be B (squaring) and the two may overlap; C is stored tile by tile while other workgroups
  * still read those rows of A and B, so C may share no word with either, with or without `accumulate` (-1, "overlap").  C, A and B may
  * be three disjoint column ranges of one parent.  Accepts 8-byte-aligned rows (an odd `ld` takes the plain path instead of Strassen).

@@ -249,10 +249,12 @@ static TilePlan plan_tiles_uncached(int m, int l, int n, int batch, bool packed,
   if (forced >= 0) {
     if (cfg_v8_rg(forced)) v8(forced);
     else if (older_model(m, l, n, batch, packed, forced, c)) consider(c);
-    if (!have) {  // a forced variant that cannot read this operand layout: the caller asks again unpacked
+    if (!have) {  // a forced variant that cannot read this operand layout (the caller asks again unpacked), or whose split-K scratch
+      // exceeds M4RI_HIP_SPLITK_WS_MIB: the plan carries no scratch, so the launcher runs it unsplit, and the query says so.  (`packed`
+      // is cleared in both cases, on purpose: the callers decide the layout by the variant -- cfg_reads_packed -- not by this field)
       best.cfg = forced;
       best.packed = false;
-      best.ksplit = m4rm_ksplit_for(m, l, n, batch, forced);
+      best.ksplit = 1;
       TilePlan est;  // (its time: the estimate of whole 512-row tiles, so that the level / shape planners never see a free launch)
       if (v8_model(m, l, n, batch, false, 12, 0, 0, est)) best.t = est.t;
     }

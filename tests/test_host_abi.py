@@ -534,6 +534,66 @@ def test_integration_lists_every_knob():
     assert sum(1 for e in k.values() if not e["dev"]) <= 22  # the shipped library's surface stays small (r5: + result side copy, the two elimination switches ADVICE r4 asked for, the census file, two test hooks)
 
 
+# Every variable the shipped library reads, and the tests that run under a setting of it (set by the test itself; the census file by
+# conftest.py) and compare what the library then computes with a reference
+# (test_every_shipped_switch_has_a_test: a new shipped switch cannot land without an entry here).
+_SW = "tests/test_gpu_shipped_switches.py::"
+SWITCH_TESTS = {
+    "M4RI_HIP_APACK": [_SW + "test_strassen_leaves_row_major"],
+    "M4RI_HIP_DEVICES": ["tests/test_gpu_parity.py::test_multi_device_shares_through_c_abi"],
+    "M4RI_HIP_ELIM_BLOCK_WORDS": ["tests/test_gpu_dirty_workspace.py::test_echelonize_dev", "tests/test_gpu_dirty_workspace.py::test_inverse_dev"],
+    "M4RI_HIP_ELIM_FAULT": ["tests/test_gpu_elim.py::test_lookahead_failure_is_reported_not_hung"],
+    "M4RI_HIP_ELIM_LOOKAHEAD": ["tests/test_gpu_elim.py::test_elimination_switches_of_the_shipped_library"],
+    "M4RI_HIP_ELIM_SPECULATE": ["tests/test_gpu_elim.py::test_elimination_switches_of_the_shipped_library"],
+    "M4RI_HIP_HOST_PIPELINE_BLOCKS": [_SW + "test_host_pipeline_blocks", _SW + "test_host_pipeline_two_blocks_big"],
+    "M4RI_HIP_HOST_PLAN": ["tests/test_gpu_parity.py::test_host_product_pipelined_over_slabs_of_the_inner_dimension"],
+    "M4RI_HIP_HOST_SMALL_WORK": ["tests/test_gpu_elim.py::test_invert_naive"],
+    "M4RI_HIP_KERNEL_CENSUS_FILE": ["tests/test_zz_kernel_census.py::test_every_kernel_of_the_library_was_launched"],
+    "M4RI_HIP_M4RM_CFG": [_SW + "test_forced_tile_variant", _SW + "test_tile_variant_outside_the_accepted_list",
+                          _SW + "test_no_scratch_for_a_forced_split_k_variant"],
+    "M4RI_HIP_PIN_CACHE_BYTES": [_SW + "test_pinned_host_blocks"],
+    "M4RI_HIP_PIN_MIN_BYTES": [_SW + "test_pinned_host_blocks"],
+    "M4RI_HIP_PLAIN_APACK": [_SW + "test_plain_products_never_pack"],
+    "M4RI_HIP_RESULT_SIDE_COLS": ["tests/test_gpu_parity.py::test_result_side_copy_can_be_switched_off"],
+    "M4RI_HIP_SPLITK_WS_MIB": [_SW + "test_no_scratch_for_partial_tiles", _SW + "test_no_scratch_for_a_forced_split_k_variant"],
+    "M4RI_HIP_STRASSEN_FUSE3": ["tests/test_gpu_parity.py::test_strassen_level_plans"],
+    "M4RI_HIP_STRASSEN_LEAF_MIN": [_SW + "test_strassen_leaf_min"],
+    "M4RI_HIP_STRASSEN_MAX_LEVELS": [_SW + "test_strassen_max_levels"],
+    "M4RI_HIP_STRASSEN_PAD": [_SW + "test_strassen_padding_switched_off"],
+    "M4RI_HIP_TRANSPOSE_GPU_MIN_BITS": [_SW + "test_every_host_transpose_on_the_device"],
+    "M4RI_HIP_TRSM_BLOCK": ["tests/test_gpu_trsm.py::test_other_block_sizes"],
+}
+
+
+# a variable that is set for its test by another file than the test's own
+SWITCH_SET_IN = {"M4RI_HIP_KERNEL_CENSUS_FILE": "tests/conftest.py"}
+
+
+def test_every_shipped_switch_has_a_test():
+    """The closed list: every variable of the first generated table of INTEGRATION.md section 6 ("Read by the shipped library") names,
+    in SWITCH_TESTS, at least one test; every test named there exists, and its file names the variable where it sets it (a setenv, an
+    entry of an environment dict, or a parameter set handed to one; SWITCH_SET_IN: the census file is set by conftest.py)."""
+    import re
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    sec = doc[doc.index("<!-- knob table: begin"):doc.index("<!-- knob table: end")]
+    shipped = sec.split("**Development builds only")[0]
+    listed = re.findall(r"^\| `(M4RI_HIP_[A-Z0-9_]+)` \|", shipped, flags=re.M)
+    assert len(listed) >= 22 and len(set(listed)) == len(listed), listed
+    sources = {}
+    for name in listed:
+        assert SWITCH_TESTS.get(name), "%s is read by the shipped library and no test is named for it in SWITCH_TESTS" % name
+        for test_id in SWITCH_TESTS[name]:
+            path, _, test = test_id.partition("::")
+            assert path.startswith("tests/test_") and test.startswith("test_"), test_id
+            if path not in sources:
+                sources[path] = open(os.path.join(ROOT, path)).read()
+            assert re.search(r"^def %s\(" % re.escape(test), sources[path], flags=re.M), "%s: no such test (%s)" % (test_id, name)
+            sets = r"""(setenv\(\s*|environ\[\s*|environ,\s*|[{,]\s*)["']?%s["']?\s*(,|\]\s*=[^=]|=[^=]|:)""" % name
+            where = SWITCH_SET_IN.get(name, path)
+            assert re.search(sets, open(os.path.join(ROOT, where)).read()), "%s: %s never sets %s" % (test_id, where, name)
+    assert not set(SWITCH_TESTS) - set(listed), "SWITCH_TESTS names variables the shipped library does not read: %s" % sorted(set(SWITCH_TESTS) - set(listed))
+
+
 def test_no_cross_lane_swaps_in_inline_asm():
     """v_permlane16_swap / v_permlane32_swap need two wait states after a VALU write of an operand (gfx950); the compiler pads
     only instructions it can see, so in the product sources they are builtins, never inline asm (round 4: the asm form in the

@@ -21,7 +21,7 @@ DESCRIPTIONS = {
     "M4RI_HIP_ELIM_BLOCK_WORDS": "64-bit word columns per elimination block (default 32 = 2048 columns)",
     "M4RI_HIP_STRASSEN_FUSE3": "0: the round-1 level plans (pairs of fused levels) instead of three fused levels and a virtual fourth",
     "M4RI_HIP_STRASSEN_PAD": "0: shapes that do not divide run as plain M4RM instead of padded / peeled Strassen plans",
-    "M4RI_HIP_STRASSEN_MAX_LEVELS": "cap of the automatic Strassen level count",
+    "M4RI_HIP_STRASSEN_MAX_LEVELS": "cap of the automatic Strassen level count (0: never automatic levels); an explicit level count -- `param` of gf2_mul_dev, the cutoff of mzd_mul -- is honoured as given, up to 6",
     "M4RI_HIP_STRASSEN_LEAF_MIN": "smallest leaf dimension the automatic level choice accepts (mzd_mul's cutoff argument overrides it)",
     "M4RI_HIP_SPLITK_WS_MIB": "cap of the per-stream scratch for partial tiles (stream-K / split-K), MiB",
     "M4RI_HIP_HOST_PIPELINE_BLOCKS": "row blocks of the host upload / multiply / download pipeline (default 4; < 2 switches it off)",
@@ -34,7 +34,7 @@ DESCRIPTIONS = {
     "M4RI_HIP_ELIM_FAULT": "test hook: 1 = update workgroup 0 of every look-ahead launch never raises its counters, so that the look-ahead workgroup's bounded wait runs out and the elimination reports the failure (tests/test_gpu_elim.py::test_lookahead_failure_is_reported_not_hung)",
     "M4RI_HIP_HOST_PLAN": "schedule of a large product on host matrices: 0 = the one the time model ends first (default), 1 = row blocks of A and C, 2-12 = the slab schedules in the numbering of gf2_host_plan_model (include/m4ri_hip.h); read per call (parity tests run every schedule)",
     "M4RI_HIP_TRSM_BLOCK": "rows of a diagonal block of the triangular solves (64, 128, 256 or 512; anything else: the default 512, DESIGN 7.3); read per call (tools/trsm_bench.py sweeps it, the tests run every value)",
-    "M4RI_HIP_M4RM_CFG": "force one tile-kernel variant (7, 8, 9-12, 20, 81, 82) for A/B runs; anything else is ignored with a message",
+    "M4RI_HIP_M4RM_CFG": "force one tile-kernel variant (7, 8, 9-12, 20, 81, 82) for A/B runs; anything else is ignored with a message.  A forced 7 / 8 / 20 / 81 / 82 whose split-K scratch exceeds M4RI_HIP_SPLITK_WS_MIB runs unsplit, and gf2_tile_plan reports ksplit 1",
 }
 
 
