@@ -1,5 +1,6 @@
 // api_internal.h -- the runtime every translation unit of the library shares (runtime_host.cpp unless noted): error state, pooled
-// device memory, per-stream scratch, streams, and the host <-> device copies.  The launch planner has its own header (mul_plan.h).
+// device memory, per-stream scratch, streams, and the host <-> device copies, and nothing else: the launch planner has its own header
+// (mul_plan.h), the argument and aliasing rules of the device-resident entries theirs (dev_args.h).
 #pragma once
 [[noreturn]] void gf2_die(const char *msg);
 #include "../../include/m4ri_hip.h"
@@ -39,67 +40,22 @@ int gf2_fail_hip(hipError_t e, const char *what);
     if (_rc) return _rc; \
   } while (0)
 int gf2_require_device();  // 0, or the "no usable HIP device" error
-
-// ---- the argument and aliasing rules of the device-resident entries (include/m4ri_hip.h section 2), one copy of each.  Everything
-// here is plain host arithmetic: the entries check their arguments before a device is required.
-inline int gf2_bad_arg(const char *fn, const std::string &what) { return gf2_fail_msg((std::string(fn) + ": " + what).c_str()); }
-// a matrix argument that can be addressed: `name` goes into the message
-inline int gf2_check_mat(const char *fn, const char *name, gf2_dmat const *M) {
-  const std::string n(name);
-  if (!M) return gf2_bad_arg(fn, n + " is null");
-  if (M->nrows < 0 || M->ncols < 0) return gf2_bad_arg(fn, n + " has a negative dimension");
-  if (M->nrows > 0 && M->ncols > 0) {
-    if (!M->data) return gf2_bad_arg(fn, n + ".data is null");
-    if (reinterpret_cast<uintptr_t>(M->data) & 7) return gf2_bad_arg(fn, n + ".data is not 8-byte aligned");
-    if (M->ld < (((long long)M->ncols + 63) >> 6))
-      return gf2_bad_arg(fn, n + ".ld is smaller than the row width (the row stride cannot hold a row)");
-  }
-  return 0;
-}
-// Do two rectangles of bits share a bit?  Rectangle X is xrows rows of xcols bits whose first bit has the bit address x0 (8 * byte
-// address + bit in the word) and whose rows lie ldx words apart; Y likewise.  Both are non-empty and no wider than their stride.  With
-// one stride a bit's address is row * L + column (L = 64 * ld), whatever parent the two views were cut from, so the answer is exact:
-// with y0 - x0 = e L + f, 0 <= f < L, row j of Y starts f bits into row j + e of X and may run on into row j + e + 1.  With different
-// strides the word ranges of the two rectangles are compared: conservative.
-inline bool gf2_bit_rects_share(__int128 x0, long long ldx, long long xrows, long long xcols, __int128 y0, long long ldy, long long yrows,
-                                long long ycols) {
-  const __int128 L = (__int128)ldx * 64;
-  if (ldx == ldy && L > 0 && xcols <= L && ycols <= L) {
-    const __int128 x = y0 - x0;
-    __int128 e = x / L, f = x % L;
-    if (f < 0) {
-      f += L;
-      e -= 1;
-    }
-    const bool same = (e < xrows && -e < yrows) && f < xcols;
-    const bool next = (e + 1 < xrows && -(e + 1) < yrows) && L - f < ycols;
-    return same || next;
-  }
-  const __int128 x1 = x0 + ((__int128)(xrows - 1) * ldx) * 64 + xcols - 1, y1 = y0 + ((__int128)(yrows - 1) * ldy) * 64 + ycols - 1;
-  return (x0 >> 6) <= (y1 >> 6) && (y0 >> 6) <= (x1 >> 6);
-}
-// "Do these two views share a word?": the rule above on the whole words of two matrices (an empty matrix shares nothing)
-inline bool gf2_views_share_word(gf2_dmat const *X, gf2_dmat const *Y) {
-  if (X->nrows <= 0 || X->ncols <= 0 || Y->nrows <= 0 || Y->ncols <= 0) return false;
-  return gf2_bit_rects_share((__int128)reinterpret_cast<uintptr_t>(X->data) * 8, X->ld, X->nrows, (((long long)X->ncols + 63) >> 6) * 64,
-                             (__int128)reinterpret_cast<uintptr_t>(Y->data) * 8, Y->ld, Y->nrows, (((long long)Y->ncols + 63) >> 6) * 64);
-}
-// one matrix under two names: what gf2_add_dev accepts as "in place"
-inline bool gf2_same_view(gf2_dmat const *X, gf2_dmat const *Y) {
-  return X->data == Y->data && X->ld == Y->ld && X->nrows == Y->nrows && X->ncols == Y->ncols;
-}
-// the refusal of a written matrix W that shares a word with another argument R of the call
-inline int gf2_refuse_overlap(const char *fn, const char *w, gf2_dmat const *W, const char *r, gf2_dmat const *R) {
-  if (!gf2_views_share_word(W, R)) return 0;
-  return gf2_bad_arg(fn, std::string(w) + " and " + r + " overlap: " + w + " is written and may share no word with " + r +
-                             " (with different ld: their address ranges may not meet)");
-}
-// scratch from the per-stream arena (grown on demand, reused by later calls on the stream, released by gf2_trim).  Slot 0: Strassen
-// operand arena / transposed operand of the naive entry; 1: split-K and stream-K partial tiles; 2: packed A; 3: the copies of a padded
-// product; 4 / 5: gf2_trsm.hip (block inverses / a leaf's result); 6 / 7: gather/gather_host.cpp (S^T / the gathered rows of the composed
-// column gather); 8 / 9: weight/weight_host.cpp (per-band column sums / block counts of the selection); 10: wht/wht_host.cpp (the
-// per-workgroup minima of gf2_min_weight_dev)
-int gf2_stream_scratch(hipStream_t s, size_t bytes, void **out, int slot = 0);
+// scratch from the per-stream arena (grown on demand, reused by later calls on the stream, released by gf2_trim).  A slot belongs to one
+// user: two that named the same one would share an arena on a stream.
+enum Gf2ScratchSlot {
+  GF2_SLOT_OPERANDS = 0,               // Strassen operand arena / transposed operand of the naive entry
+  GF2_SLOT_PARTIAL_TILES = 1,          // split-K and stream-K partial tiles
+  GF2_SLOT_PACKED_A = 2,               // packed A
+  GF2_SLOT_PADDED = 3,                 // the copies of a padded product
+  GF2_SLOT_TRSM_INVERSES = 4,          // gf2_trsm.hip: block inverses
+  GF2_SLOT_TRSM_LEAF = 5,              // gf2_trsm.hip: a leaf's result
+  GF2_SLOT_GATHER_TRANSPOSED = 6,      // gather/gather_host.cpp: S^T
+  GF2_SLOT_GATHER_ROWS = 7,            // gather/gather_host.cpp: the gathered rows of the composed column gather
+  GF2_SLOT_WEIGHT_COL_PARTIALS = 8,    // weight/weight_host.cpp: per-band column sums
+  GF2_SLOT_WEIGHT_SELECT_COUNTS = 9,   // weight/weight_host.cpp: block counts of the selection
+  GF2_SLOT_WHT_MIN_PARTIALS = 10,      // wht/wht_host.cpp: the per-workgroup minima of gf2_min_weight_dev
+};
+int gf2_stream_scratch(hipStream_t s, size_t bytes, void **out, int slot);  // slot: a Gf2ScratchSlot
 // counts a run of a host routine of the size dispatch (gf2_host_small_calls)
 void gf2_note_host_small_call();
 // pooled device memory.  gf2_dev_free is NOT stream-ordered: the caller guarantees that no queued work still touches the block (it

@@ -1,0 +1,103 @@
+// dev_args.h -- the argument and aliasing rules of the device-resident entries (include/m4ri_hip.h section 2 and the companion
+// headers), one copy of each.  Everything here is plain host arithmetic: the entries check their arguments before a device is required
+// and before the first HIP call, so a bad call fails the same way with and without a device.  The checks of one module alone (limits
+// and texts of their own) stay with that module and are built from these.
+#pragma once
+#include <stdint.h>
+
+#include <string>
+
+#include "api_internal.h"
+
+inline int gf2_bad_arg(const char *fn, const std::string &what) { return gf2_fail_msg((std::string(fn) + ": " + what).c_str()); }
+// a pointer argument: "<name> is null", "<name> is not <N>-byte aligned" (align: a power of two).  Entries that accept a null pointer
+// under some condition call the two halves on their own, in their own order.  (static, here and below: a helper that the library's
+// table of exported symbols does not list already stays out of it)
+static inline int gf2_refuse_null(const char *fn, const std::string &name, const void *p) {
+  return p ? 0 : gf2_bad_arg(fn, name + " is null");
+}
+static inline int gf2_refuse_misaligned(const char *fn, const std::string &name, const void *p, int align) {
+  if (!(reinterpret_cast<uintptr_t>(p) & (uintptr_t)(align - 1))) return 0;
+  return gf2_bad_arg(fn, name + " is not " + std::to_string(align) + "-byte aligned");
+}
+static inline int gf2_check_ptr(const char *fn, const std::string &name, const void *p, int align) {
+  if (int rc = gf2_refuse_null(fn, name, p)) return rc;
+  return gf2_refuse_misaligned(fn, name, p, align);
+}
+// a matrix argument that can be addressed: `name` goes into the message
+inline int gf2_check_mat(const char *fn, const char *name, gf2_dmat const *M) {
+  const std::string n(name);
+  GF2_RC(gf2_refuse_null(fn, n, M));
+  if (M->nrows < 0 || M->ncols < 0) return gf2_bad_arg(fn, n + " has a negative dimension");
+  if (M->nrows > 0 && M->ncols > 0) {
+    GF2_RC(gf2_check_ptr(fn, n + ".data", M->data, 8));
+    if (M->ld < (((long long)M->ncols + 63) >> 6))
+      return gf2_bad_arg(fn, n + ".ld is smaller than the row width (the row stride cannot hold a row)");
+  }
+  return 0;
+}
+// the device check of an entry whose messages carry its name (the products answer with gf2_require_device's text)
+static inline int gf2_require_device_for(const char *fn) { return gf2_device_count() > 0 ? 0 : gf2_bad_arg(fn, "no usable HIP device"); }
+// what an entry returns after its last launch
+static inline int gf2_hip_rc(hipError_t e, const char *what) { return e == hipSuccess ? 0 : gf2_fail_hip(e, what); }
+
+// Do two rectangles of bits share a bit?  Rectangle X is xrows rows of xcols bits whose first bit has the bit address x0 (8 * byte
+// address + bit in the word) and whose rows lie ldx words apart; Y likewise.  Both are non-empty and no wider than their stride.  With
+// one stride a bit's address is row * L + column (L = 64 * ld), whatever parent the two views were cut from, so the answer is exact:
+// with y0 - x0 = e L + f, 0 <= f < L, row j of Y starts f bits into row j + e of X and may run on into row j + e + 1.  With different
+// strides the word ranges of the two rectangles are compared: conservative.
+inline bool gf2_bit_rects_share(__int128 x0, long long ldx, long long xrows, long long xcols, __int128 y0, long long ldy, long long yrows,
+                                long long ycols) {
+  const __int128 L = (__int128)ldx * 64;
+  if (ldx == ldy && L > 0 && xcols <= L && ycols <= L) {
+    const __int128 x = y0 - x0;
+    __int128 e = x / L, f = x % L;
+    if (f < 0) {
+      f += L;
+      e -= 1;
+    }
+    const bool same = (e < xrows && -e < yrows) && f < xcols;
+    const bool next = (e + 1 < xrows && -(e + 1) < yrows) && L - f < ycols;
+    return same || next;
+  }
+  const __int128 x1 = x0 + ((__int128)(xrows - 1) * ldx) * 64 + xcols - 1, y1 = y0 + ((__int128)(yrows - 1) * ldy) * 64 + ycols - 1;
+  return (x0 >> 6) <= (y1 >> 6) && (y0 >> 6) <= (x1 >> 6);
+}
+// "Do these two views share a word?": the rule above on the whole words of two matrices (an empty matrix shares nothing)
+inline bool gf2_views_share_word(gf2_dmat const *X, gf2_dmat const *Y) {
+  if (X->nrows <= 0 || X->ncols <= 0 || Y->nrows <= 0 || Y->ncols <= 0) return false;
+  return gf2_bit_rects_share((__int128)reinterpret_cast<uintptr_t>(X->data) * 8, X->ld, X->nrows, (((long long)X->ncols + 63) >> 6) * 64,
+                             (__int128)reinterpret_cast<uintptr_t>(Y->data) * 8, Y->ld, Y->nrows, (((long long)Y->ncols + 63) >> 6) * 64);
+}
+// one matrix under two names: what gf2_add_dev accepts as "in place"
+inline bool gf2_same_view(gf2_dmat const *X, gf2_dmat const *Y) {
+  return X->data == Y->data && X->ld == Y->ld && X->nrows == Y->nrows && X->ncols == Y->ncols;
+}
+// the refusal of a written matrix W that shares a word with another argument R of the call
+inline int gf2_refuse_overlap(const char *fn, const char *w, gf2_dmat const *W, const char *r, gf2_dmat const *R) {
+  if (!gf2_views_share_word(W, R)) return 0;
+  return gf2_bad_arg(fn, std::string(w) + " and " + r + " overlap: " + w + " is written and may share no word with " + r +
+                             " (with different ld: their address ranges may not meet)");
+}
+
+// Flat arrays (indices, weights, counts) know no rows: they are compared by address range, and so is a matrix against one of them --
+// from its first word to the last word of its last row, the padding of the rows in between included.  An empty range meets nothing.
+static inline bool gf2_ranges_meet(const void *p, long long pbytes, const void *q, long long qbytes) {
+  const __int128 a0 = reinterpret_cast<uintptr_t>(p), a1 = a0 + pbytes;
+  const __int128 b0 = reinterpret_cast<uintptr_t>(q), b1 = b0 + qbytes;
+  return pbytes > 0 && qbytes > 0 && a0 < b1 && b0 < a1;
+}
+// one past the last byte of the words of a non-empty matrix
+static inline __int128 gf2_mat_end(gf2_dmat const *M) {
+  return (__int128)reinterpret_cast<uintptr_t>(M->data) + 8 * ((__int128)(M->nrows - 1) * M->ld + (((long long)M->ncols + 63) >> 6));
+}
+static inline bool gf2_range_meets_mat(const void *p, long long bytes, gf2_dmat const *M) {
+  if (M->nrows <= 0 || M->ncols <= 0 || bytes <= 0) return false;
+  const __int128 a0 = reinterpret_cast<uintptr_t>(p), a1 = a0 + bytes;
+  return a0 < gf2_mat_end(M) && (__int128)reinterpret_cast<uintptr_t>(M->data) < a1;
+}
+// two matrices by address range, whatever their strides (gf2_inverse_batch_dev: its kernel owns whole stacks)
+static inline bool gf2_mat_ranges_meet(gf2_dmat const *X, gf2_dmat const *Y) {
+  if (X->nrows <= 0 || X->ncols <= 0 || Y->nrows <= 0 || Y->ncols <= 0) return false;
+  return (__int128)reinterpret_cast<uintptr_t>(X->data) < gf2_mat_end(Y) && (__int128)reinterpret_cast<uintptr_t>(Y->data) < gf2_mat_end(X);
+}

@@ -6,7 +6,7 @@
 
 #include <string>
 
-#include "api_internal.h"
+#include "dev_args.h"
 #include "gf2_kernels.h"
 
 namespace {
@@ -15,30 +15,20 @@ constexpr int kMaxRows = 512, kMaxCols = 1024, kWaveRows = 64, kWaveThreads = GF
 
 inline long long words_of(long long bits) { return (bits + 63) >> 6; }
 
-int bad(const char *fn, const std::string &what) { return gf2_fail_msg((std::string(fn) + ": " + what).c_str()); }
-
 // a stack of matrices of m rows that the kernels can address; 0 or -1 (gf2_last_error is set)
 int check_stack(const char *fn, const char *name, gf2_dmat const *M, int m) {
   const std::string n(name);
-  if (!M) return bad(fn, n + " is null");
-  if (m < 1 || m > kMaxRows) return bad(fn, "matrices of " + std::to_string(m) + " rows are outside the limits (1 .. 512 rows)");
+  GF2_RC(gf2_refuse_null(fn, n, M));
+  if (m < 1 || m > kMaxRows) return gf2_bad_arg(fn, "matrices of " + std::to_string(m) + " rows are outside the limits (1 .. 512 rows)");
   if (M->ncols < 1 || M->ncols > kMaxCols)
-    return bad(fn, n + " has " + std::to_string(M->ncols) + " columns: outside the limits (1 .. 1024 columns; gf2_echelonize_dev has none)");
-  if (M->nrows < 0) return bad(fn, n + " has a negative row count");
-  if (M->nrows % m) return bad(fn, n + ".nrows is not a multiple of the matrices' row count");
+    return gf2_bad_arg(fn, n + " has " + std::to_string(M->ncols) +
+                               " columns: outside the limits (1 .. 1024 columns; gf2_echelonize_dev has none)");
+  if (M->nrows < 0) return gf2_bad_arg(fn, n + " has a negative row count");
+  if (M->nrows % m) return gf2_bad_arg(fn, n + ".nrows is not a multiple of the matrices' row count");
   if (M->nrows == 0) return 0;
-  if (!M->data) return bad(fn, n + ".data is null");
-  if (M->ld < words_of(M->ncols)) return bad(fn, n + ".ld is smaller than the row width");
-  if (reinterpret_cast<uintptr_t>(M->data) & 7) return bad(fn, n + ".data is not 8-byte aligned");
-  return 0;
-}
-
-int no_device(const char *fn) { return gf2_device_count() > 0 ? 0 : bad(fn, "no usable HIP device"); }
-
-// first and one-past-last byte of the words a stack's rows occupy
-void byte_range(gf2_dmat const *M, uintptr_t *lo, uintptr_t *hi) {
-  *lo = reinterpret_cast<uintptr_t>(M->data);
-  *hi = *lo + (uintptr_t)(((long long)(M->nrows - 1) * M->ld + words_of(M->ncols)) * 8);
+  GF2_RC(gf2_refuse_null(fn, n + ".data", M->data));
+  if (M->ld < words_of(M->ncols)) return gf2_bad_arg(fn, n + ".ld is smaller than the row width");
+  return gf2_refuse_misaligned(fn, n + ".data", M->data, 8);
 }
 
 }  // namespace
@@ -75,29 +65,24 @@ extern "C" int gf2_elim_batch_plan(int m, int ncols, int inverse, long long out[
 extern "C" int gf2_echelonize_batch_dev(gf2_dmat *A, int m, int full, int ncols_limit, int *ranks, int *pivot_cols, void *stream) {
   static const char fn[] = "gf2_echelonize_batch_dev";
   if (int rc = check_stack(fn, "A", A, m)) return rc;
-  if (ncols_limit < 0) return bad(fn, "ncols_limit is negative");
+  if (ncols_limit < 0) return gf2_bad_arg(fn, "ncols_limit is negative");
   if (A->nrows == 0) return 0;
-  if (int rc = no_device(fn)) return rc;
+  GF2_RC(gf2_require_device_for(fn));
   const int limit = (ncols_limit > 0 && ncols_limit < A->ncols) ? ncols_limit : A->ncols;
-  hipError_t e = gf2k_elim_batch(A->data, A->ld, A->data, A->ld, m, A->ncols, limit, full ? 1 : 0, 0, A->nrows / m, ranks, pivot_cols,
-                                 nullptr, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+  return gf2_hip_rc(gf2k_elim_batch(A->data, A->ld, A->data, A->ld, m, A->ncols, limit, full ? 1 : 0, 0, A->nrows / m, ranks, pivot_cols,
+                                    nullptr, static_cast<hipStream_t>(stream)), fn);
 }
 
 extern "C" int gf2_inverse_batch_dev(gf2_dmat *Ainv, gf2_dmat const *A, int n, int *singular, void *stream) {
   static const char fn[] = "gf2_inverse_batch_dev";
   if (int rc = check_stack(fn, "A", A, n)) return rc;
-  if (A->ncols != n) return bad(fn, "the blocks of A must be n x n (A.ncols != n)");
-  if (!Ainv) return bad(fn, "Ainv is null");
-  if (Ainv->nrows != A->nrows || Ainv->ncols != A->ncols) return bad(fn, "Ainv must have the shape of A");
+  if (A->ncols != n) return gf2_bad_arg(fn, "the blocks of A must be n x n (A.ncols != n)");
+  GF2_RC(gf2_refuse_null(fn, "Ainv", Ainv));
+  if (Ainv->nrows != A->nrows || Ainv->ncols != A->ncols) return gf2_bad_arg(fn, "Ainv must have the shape of A");
   if (int rc = check_stack(fn, "Ainv", Ainv, n)) return rc;
   if (A->nrows == 0) return 0;
-  uintptr_t a0, a1, i0, i1;
-  byte_range(A, &a0, &a1);
-  byte_range(Ainv, &i0, &i1);
-  if (a0 < i1 && i0 < a1) return bad(fn, "the address ranges of A and Ainv overlap");
-  if (int rc = no_device(fn)) return rc;
-  hipError_t e = gf2k_elim_batch(A->data, A->ld, Ainv->data, Ainv->ld, n, n, n, 1, 1, A->nrows / n, nullptr, nullptr, singular,
-                                 static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+  if (gf2_mat_ranges_meet(A, Ainv)) return gf2_bad_arg(fn, "the address ranges of A and Ainv overlap");
+  GF2_RC(gf2_require_device_for(fn));
+  return gf2_hip_rc(gf2k_elim_batch(A->data, A->ld, Ainv->data, Ainv->ld, n, n, n, 1, 1, A->nrows / n, nullptr, nullptr, singular,
+                                    static_cast<hipStream_t>(stream)), fn);
 }

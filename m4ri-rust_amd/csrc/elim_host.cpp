@@ -7,7 +7,7 @@
 #include <cstdlib>
 #include <map>
 
-#include "api_internal.h"
+#include "dev_args.h"
 #include "gf2_kernels.h"
 #include "gf2_env.h"
 
@@ -172,7 +172,7 @@ static int echelonize_dev(gf2_dmat *A, int full, int col_limit, int *rank_out, i
 extern "C" int gf2_echelonize_dev(gf2_dmat *A, int full, int ncols_limit, int *rank, int *pivot_cols, void *stream) {
   static const char fn[] = "gf2_echelonize_dev";
   if (int rc = gf2_check_mat(fn, "A", A)) return rc;
-  if (!rank) return gf2_bad_arg(fn, "rank is null");
+  GF2_RC(gf2_refuse_null(fn, "rank", rank));
   *rank = 0;
   if (A->nrows == 0 || A->ncols == 0) return 0;
   if (int rc = gf2_require_device()) return rc;
@@ -216,7 +216,7 @@ static int inverse_dev(gf2_dmat *Ainv, const u64 *Adata, long long lda, bool a_o
 extern "C" int gf2_inverse_dev(gf2_dmat *Ainv, gf2_dmat const *A, int *singular, void *stream) {
   static const char fn[] = "gf2_inverse_dev";
   if (gf2_check_mat(fn, "Ainv", Ainv) || gf2_check_mat(fn, "A", A)) return -1;
-  if (!singular) return gf2_bad_arg(fn, "singular is null");
+  GF2_RC(gf2_refuse_null(fn, "singular", singular));
   if (A->nrows != A->ncols || Ainv->nrows != A->nrows || Ainv->ncols != A->ncols)
     return gf2_bad_arg(fn, "matrices must be square and of equal size");
   *singular = 0;

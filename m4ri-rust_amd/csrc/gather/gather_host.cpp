@@ -7,23 +7,12 @@
 #include <string>
 
 #include "../../../include/m4ri_hip_gather.h"
-#include "../api_internal.h"
+#include "../dev_args.h"
 #include "../gf2_kernels.h"
 #include "gather_plan.h"
 #include "gf2_gather.h"
 
 namespace {
-
-// scratch slots of the composed column route (api_internal.h lists 0 .. 5)
-constexpr int kSlotTransposed = 6, kSlotGathered = 7;
-
-// do the `bytes` bytes at p meet the words of M?  (M is non-empty)
-bool range_meets(const void *p, long long bytes, gf2_dmat const *M) {
-  const __int128 a0 = reinterpret_cast<uintptr_t>(p), a1 = a0 + bytes;
-  const __int128 m0 = reinterpret_cast<uintptr_t>(M->data);
-  const __int128 m1 = m0 + 8 * ((__int128)(M->nrows - 1) * M->ld + (((long long)M->ncols + 63) >> 6));
-  return a0 < m1 && m0 < a1;
-}
 
 // 0: go ahead; 1: nothing to do; -1: refused (gf2_last_error is set).  count: the ints idx holds
 int check_call(const char *fn, gf2_dmat *D, gf2_dmat const *S, const int *idx, long long count, const int *bad, bool rows) {
@@ -32,12 +21,11 @@ int check_call(const char *fn, gf2_dmat *D, gf2_dmat const *S, const int *idx, l
     return gf2_bad_arg(fn, rows ? "shape mismatch: D and S must have equal column counts (D.ncols != S.ncols)"
                                 : "shape mismatch: D and S must have equal row counts (D.nrows != S.nrows)");
   if (D->nrows == 0 || D->ncols == 0) return 1;
-  if (!idx) return gf2_bad_arg(fn, "idx is null");
-  if (reinterpret_cast<uintptr_t>(idx) & 3) return gf2_bad_arg(fn, "idx is not 4-byte aligned");
-  if (bad && (reinterpret_cast<uintptr_t>(bad) & 3)) return gf2_bad_arg(fn, "bad is not 4-byte aligned");
+  GF2_RC(gf2_check_ptr(fn, "idx", idx, 4));
+  if (bad) GF2_RC(gf2_refuse_misaligned(fn, "bad", bad, 4));
   if (gf2_refuse_overlap(fn, "D", D, "S", S)) return -1;
-  if (range_meets(idx, 4 * count, D)) return gf2_bad_arg(fn, "idx and D overlap: the address range of idx may not meet D's");
-  if (bad && range_meets(bad, 4, D)) return gf2_bad_arg(fn, "bad and D overlap: the address of bad may not lie in D's address range");
+  if (gf2_range_meets_mat(idx, 4 * count, D)) return gf2_bad_arg(fn, "idx and D overlap: the address range of idx may not meet D's");
+  if (bad && gf2_range_meets_mat(bad, 4, D)) return gf2_bad_arg(fn, "bad and D overlap: the address of bad may not lie in D's address range");
   return 0;
 }
 
@@ -49,7 +37,7 @@ extern "C" int gf2_gather_rows_dev(gf2_dmat *D, gf2_dmat const *S, const int *id
   GF2_RC(gf2_require_device());
   const hipError_t e = gf2k_gather_rows(D->data, D->ld, S->data, S->ld, D->nrows, S->nrows, D->ncols, idx, accumulate, bad,
                                         static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+  return gf2_hip_rc(e, fn);
 }
 
 extern "C" int gf2_gather_cols_dev(gf2_dmat *D, gf2_dmat const *S, const int *idx, int *bad, void *stream) {
@@ -60,19 +48,19 @@ extern "C" int gf2_gather_cols_dev(gf2_dmat *D, gf2_dmat const *S, const int *id
   const GatherColsPlan plan = gather_cols_plan(D->nrows, S->ncols, D->ncols);
   if (plan.path == 0) {
     const hipError_t e = gf2k_gather_cols(D->data, D->ld, D->ncols, S->data, S->ld, S->ncols, D->nrows, idx, bad, s);
-    return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+    return gf2_hip_rc(e, fn);
   }
   // composed: T = S^T, G[j] = T[idx[j]], D = G^T, all on s; the two scratch matrices stay with the stream for the next call
   std::lock_guard<std::mutex> lk(gf2_enqueue_mu);  // another thread on the same stream would be handed the same scratch
   const long long ldt = gather_ld_for(D->nrows);
   void *pt = nullptr, *pg = nullptr;
-  GF2_RC(gf2_stream_scratch(s, (size_t)(8 * ldt * S->ncols), &pt, kSlotTransposed));
-  GF2_RC(gf2_stream_scratch(s, (size_t)(8 * ldt * D->ncols), &pg, kSlotGathered));
+  GF2_RC(gf2_stream_scratch(s, (size_t)(8 * ldt * S->ncols), &pt, GF2_SLOT_GATHER_TRANSPOSED));
+  GF2_RC(gf2_stream_scratch(s, (size_t)(8 * ldt * D->ncols), &pg, GF2_SLOT_GATHER_ROWS));
   uint64_t *T = static_cast<uint64_t *>(pt), *G = static_cast<uint64_t *>(pg);
   hipError_t e = gf2k_transpose(T, ldt, S->data, S->ld, S->nrows, S->ncols, s);
   if (e == hipSuccess) e = gf2k_gather_rows(G, ldt, T, ldt, D->ncols, S->ncols, D->nrows, idx, 0, bad, s);
   if (e == hipSuccess) e = gf2k_transpose(D->data, D->ld, G, ldt, D->ncols, D->nrows, s);
-  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+  return gf2_hip_rc(e, fn);
 }
 
 extern "C" int gf2_gather_cols_plan(int nrows, int s_ncols, int d_ncols, long long out[4]) {

@@ -18,7 +18,7 @@
 // Every word of K is written, the excess bits of its last word as zeros (a compress leaves zeros above the bits it gathered).
 #include <hip/hip_runtime.h>
 
-#include "api_internal.h"
+#include "dev_args.h"
 #include "gf2_kernels.h"
 
 typedef uint64_t u64;
@@ -135,10 +135,10 @@ struct EventPair {
 extern "C" int gf2_nullspace_dev(gf2_dmat *A, gf2_dmat *K, int *rank, int *pivot_cols, void *stream) {
   static const char fn[] = "gf2_nullspace_dev";
   if (int rc = gf2_check_mat(fn, "A", A)) return rc;
-  if (!K) return gf2_bad_arg(fn, "K is null");
-  if (!rank) return gf2_bad_arg(fn, "rank is null");
+  GF2_RC(gf2_refuse_null(fn, "K", K));
+  GF2_RC(gf2_refuse_null(fn, "rank", rank));
   const int n = A->ncols, nw = words_of(n);
-  if (n > 0 && gf2_device_count() <= 0) return gf2_bad_arg(fn, "no usable HIP device");
+  if (n > 0) GF2_RC(gf2_require_device_for(fn));
   hipStream_t s = static_cast<hipStream_t>(stream);
   *rank = 0;
   *K = gf2_dmat{nullptr, 0, n, 0};

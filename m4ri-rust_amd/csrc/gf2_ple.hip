@@ -17,7 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "api_internal.h"
+#include "dev_args.h"
 #include "gf2_kernels.h"
 
 typedef uint64_t u64;
@@ -406,11 +406,11 @@ extern "C" int gf2_apply_p_dev(gf2_dmat *A, const int *P, int len, int right, in
   static const char fn[] = "gf2_apply_p_dev";
   if (int rc = gf2_check_mat(fn, "A", A)) return rc;
   if (len < 0) return gf2_bad_arg(fn, "len is negative");
-  if (len > 0 && !P) return gf2_bad_arg(fn, "P is null");
+  if (len > 0) GF2_RC(gf2_refuse_null(fn, "P", P));
   for (int i = 0, n = std::min(len, right ? A->ncols : A->nrows); i < n; ++i)
     if (P[i] < 0 || P[i] >= (right ? A->ncols : A->nrows)) return gf2_bad_arg(fn, "P[i] out of range");
   if (A->nrows == 0 || A->ncols == 0) return 0;
-  if (gf2_device_count() <= 0) return gf2_bad_arg(fn, "no usable HIP device");
+  GF2_RC(gf2_require_device_for(fn));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (!right) {  // left: ascending swaps; left_trans: descending
     return apply_rows(*A, perm_map(P, len, A->nrows, trans != 0), s);
@@ -437,14 +437,14 @@ static void sigma_to_transpositions(const std::vector<int> &sigma, int *P) {
 extern "C" int gf2_ple_dev(gf2_dmat *A, int pluq, int *P, int *Q, int *rank, void *stream) {
   static const char fn[] = "gf2_ple_dev";
   if (int rc = gf2_check_mat(fn, "A", A)) return rc;
-  if (!rank) return gf2_bad_arg(fn, "rank is null");
+  GF2_RC(gf2_refuse_null(fn, "rank", rank));
   if ((A->nrows && !P) || (A->ncols && !Q)) return gf2_bad_arg(fn, "P or Q is null");
   const int m = A->nrows, n = A->ncols;
   *rank = 0;
   for (int i = 0; i < m; ++i) P[i] = i;
   for (int j = 0; j < n; ++j) Q[j] = j;
   if (m == 0 || n == 0) return 0;
-  if (gf2_device_count() <= 0) return gf2_bad_arg(fn, "no usable HIP device");
+  GF2_RC(gf2_require_device_for(fn));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int aw = words_of(n);
   DevBuf pi, qc, sc, cand, tab, stash, eb;
@@ -500,7 +500,7 @@ extern "C" int gf2_pluq_solve_left_dev(gf2_dmat const *A, int rank, const int *P
                                        int *inconsistent, void *stream) {
   static const char fn[] = "gf2_pluq_solve_left_dev";
   if (gf2_check_mat(fn, "A", A) || gf2_check_mat(fn, "B", B)) return -1;
-  if (!inconsistent) return gf2_bad_arg(fn, "inconsistent is null");
+  GF2_RC(gf2_refuse_null(fn, "inconsistent", inconsistent));
   if ((A->nrows && !P) || (A->ncols && !Q)) return gf2_bad_arg(fn, "P or Q is null");
   const int m = A->nrows, n = A->ncols, kb = B->ncols;
   *inconsistent = 0;
@@ -512,7 +512,7 @@ extern "C" int gf2_pluq_solve_left_dev(gf2_dmat const *A, int rank, const int *P
   for (int j = 0; j < n; ++j)
     if (Q[j] < 0 || Q[j] >= n) return gf2_fail_msg("gf2_pluq_solve_left_dev: Q[j] out of range");
   if (int rc = gf2_refuse_overlap(fn, "B", B, "A", A)) return rc;  // B is rewritten step by step while A is still read
-  if (gf2_device_count() <= 0) return gf2_bad_arg(fn, "no usable HIP device");
+  GF2_RC(gf2_require_device_for(fn));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int bw = words_of(kb);
   const u64 bmask = last_mask(kb);

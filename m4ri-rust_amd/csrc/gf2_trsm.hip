@@ -17,7 +17,7 @@
 #include <cstdlib>
 #include <mutex>
 
-#include "api_internal.h"
+#include "dev_args.h"
 #include "gf2_kernels.h"
 
 typedef uint64_t u64;
@@ -235,7 +235,7 @@ extern "C" int gf2_trsm_dev(gf2_dmat const *T, gf2_dmat *B, int upper, int right
   const int n = T->nrows;
   if (n == 0 || B->nrows == 0 || B->ncols == 0) return 0;
   if (int rc = gf2_refuse_overlap(fn, "B", B, "T", T)) return rc;  // blocks of B are rewritten while later steps still read T
-  if (gf2_device_count() <= 0) return gf2_bad_arg(fn, "no usable HIP device");
+  GF2_RC(gf2_require_device_for(fn));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int d = trsm_block(n), nb = (n + d - 1) / d;
   TrsmCtx c{*T, *B, n, d, upper != 0, right != 0, nullptr, even_ld(d >> 6), nullptr, 0, s};
@@ -243,9 +243,9 @@ extern "C" int gf2_trsm_dev(gf2_dmat const *T, gf2_dmat *B, int upper, int right
   const size_t tmp_rows = right ? (size_t)B->nrows : (size_t)d;
   std::lock_guard<std::mutex> lk(g_trsm_mu);
   void *p = nullptr;
-  GF2_RC(gf2_stream_scratch(s, (size_t)nb * d * c.ldi * 8, &p, 4));
+  GF2_RC(gf2_stream_scratch(s, (size_t)nb * d * c.ldi * 8, &p, GF2_SLOT_TRSM_INVERSES));
   c.inv = static_cast<u64 *>(p);
-  GF2_RC(gf2_stream_scratch(s, tmp_rows * c.ldt * 8, &p, 5));
+  GF2_RC(gf2_stream_scratch(s, tmp_rows * c.ldt * 8, &p, GF2_SLOT_TRSM_LEAF));
   c.tmp = static_cast<u64 *>(p);
   const size_t lds_bytes = (size_t)2 * d * (d >> 6) * 8;  // 64 KiB at d = 512
   if (upper)

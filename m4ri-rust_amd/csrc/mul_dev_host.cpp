@@ -4,7 +4,7 @@
 #include <cstdint>
 #include <vector>
 
-#include "api_internal.h"
+#include "dev_args.h"
 #include "gf2_kernels.h"
 #include "mul_plan.h"
 
@@ -29,7 +29,7 @@ static int apply_tile_plan(gf2k_mul_args &a, const TilePlan &tp, hipStream_t s) 
   const size_t want = tp.scratch();  // (the launches of a plan run one after the other)
   if (want == 0) return 0;
   void *ws = nullptr;
-  if (gf2_stream_scratch(s, want, &ws, 1) != 0) return 0;
+  if (gf2_stream_scratch(s, want, &ws, GF2_SLOT_PARTIAL_TILES) != 0) return 0;
   a.P = static_cast<u64 *>(ws);
   a.p_words = (long long)(want / sizeof(u64));
   if (tp.ws_bytes == 0) return 0;
@@ -86,7 +86,7 @@ static int mul_widevec(gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B, int ac
   const int m = A->nrows, l = A->ncols, n = B->ncols;
   const long long ldbt = (words_of(l) + 1) & ~1ll;
   void *bt = nullptr;
-  if (int rc = gf2_stream_scratch(s, (size_t)n * ldbt * sizeof(u64), &bt)) return rc;
+  if (int rc = gf2_stream_scratch(s, (size_t)n * ldbt * sizeof(u64), &bt, GF2_SLOT_OPERANDS)) return rc;
   HIP_TRY(gf2k_transpose(static_cast<u64 *>(bt), ldbt, B->data, B->ld, l, n, s));
   const u64 *Bt = static_cast<const u64 *>(bt);
   const int n0 = n < 32 ? n : 32;
@@ -139,7 +139,7 @@ int gf2_mul_m4rm_plain(gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B, int ac
       const long long ldl = (words_of(l) + 1) & ~1ll, wn = words_of(n), ldn = (wn + 1) & ~1ll, ldct = (passes + 1) & ~1ll;
       const size_t wBt = (size_t)n * ldl, wAt = (size_t)l * 2, wCt = (size_t)n * ldct, wTmp = accumulate ? (size_t)m * ldn : 0;
       void *ws = nullptr;
-      if (gf2_stream_scratch(s, (wBt + wAt + wCt + wTmp) * sizeof(u64), &ws) == 0) {
+      if (gf2_stream_scratch(s, (wBt + wAt + wCt + wTmp) * sizeof(u64), &ws, GF2_SLOT_OPERANDS) == 0) {
         u64 *Bt = static_cast<u64 *>(ws), *At = Bt + wBt, *Ct = At + wAt, *Tmp = Ct + wCt;
         HIP_TRY(gf2k_transpose(Bt, ldl, B->data, B->ld, l, n, s));  // n x l
         for (int p = 0; p < passes; ++p) {
@@ -167,7 +167,7 @@ int gf2_mul_m4rm_plain(gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B, int ac
   long long lda = A->ld;
   if (packed) {
     void *pa = nullptr;
-    if (gf2_stream_scratch(s, (size_t)(prow * wp * 8), &pa, 2) == 0) {
+    if (gf2_stream_scratch(s, (size_t)(prow * wp * 8), &pa, GF2_SLOT_PACKED_A) == 0) {
       HIP_TRY(gf2k_packA(static_cast<u64 *>(pa), wp, A->data, A->ld, m, words_of(l), s));
       Aptr = static_cast<const u64 *>(pa);
       lda = wp;
@@ -207,7 +207,7 @@ static int mul_strassen(gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B, int a
   if (L > 6) L = 6;
   const StrassenArena arena = strassen_arena(m, l, n, L);
   void *ws = nullptr;
-  if (int rc = gf2_stream_scratch(s, arena.words * sizeof(u64), &ws)) return rc;
+  if (int rc = gf2_stream_scratch(s, arena.words * sizeof(u64), &ws, GF2_SLOT_OPERANDS)) return rc;
   const std::vector<PlanStep> plan = strassen_plan(L);
   u64 *Aop[7], *Bop[7], *Pop[7];  // operands and products of level i (of the levels the plan materialises)
   auto at = [&](size_t off) { return off == StrassenArena::none ? nullptr : static_cast<u64 *>(ws) + off; };
@@ -324,7 +324,7 @@ static int mul_strassen_padded(gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B
   const long long wa = lp / 64, wb = np / 64;
   const size_t wordsA = (size_t)mp * wa, wordsB = (size_t)lp * wb, wordsC = (size_t)mp * wb;
   void *ws = nullptr;
-  if (int rc = gf2_stream_scratch(s, (wordsA + wordsB + wordsC) * sizeof(u64), &ws, 3)) return rc;
+  if (int rc = gf2_stream_scratch(s, (wordsA + wordsB + wordsC) * sizeof(u64), &ws, GF2_SLOT_PADDED)) return rc;
   u64 *pa = static_cast<u64 *>(ws), *pb = pa + wordsA, *pc = pb + wordsB;
   HIP_TRY(gf2k_padcopy(pa, wa, mp, (int)wa, A->data, A->ld, m, l, s));
   HIP_TRY(gf2k_padcopy(pb, wb, lp, (int)wb, B->data, B->ld, l, n, s));
@@ -395,7 +395,7 @@ static int mul_naive_dev(gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B, int 
   const long long ldbt = (words_of(l) + 1) & ~1ll;
   const size_t bytes = (size_t)n * ldbt * sizeof(u64);
   void *bt = nullptr;
-  if (int rc = gf2_stream_scratch(s, bytes, &bt)) return rc;
+  if (int rc = gf2_stream_scratch(s, bytes, &bt, GF2_SLOT_OPERANDS)) return rc;
   hipError_t e = gf2k_transpose(static_cast<u64 *>(bt), ldbt, B->data, B->ld, l, n, s);
   if (e != hipSuccess) return gf2_fail_hip(e, "gf2k_transpose");
   e = gf2k_rowparity(A->data, A->ld, static_cast<u64 *>(bt), ldbt, C->data, C->ld, m, l, n, accumulate, s);
@@ -418,8 +418,7 @@ static int check_mul(const char *fn, const char *bname, const gf2_dmat *C, const
 // an inner dimension of 0: the product is the zero matrix
 static int mul_of_nothing(const char *fn, gf2_dmat *C, int accumulate, hipStream_t s) {
   if (accumulate) return 0;
-  const hipError_t e = gf2k_xor2d(C->data, C->ld, nullptr, 0, nullptr, 0, C->nrows, words_of(C->ncols), s);
-  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+  return gf2_hip_rc(gf2k_xor2d(C->data, C->ld, nullptr, 0, nullptr, 0, C->nrows, words_of(C->ncols), s), fn);
 }
 
 int gf2_mul_dispatch(gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B, int accumulate, int algo, int param, hipStream_t s, bool sync_free) {
@@ -519,7 +518,7 @@ extern "C" int gf2_transpose_dev(gf2_dmat *D, gf2_dmat const *S, void *stream) {
 extern "C" int gf2_equal_dev(gf2_dmat const *A, gf2_dmat const *B, int *equal, void *stream) {
   static const char fn[] = "gf2_equal_dev";
   if (gf2_check_mat(fn, "A", A) || gf2_check_mat(fn, "B", B)) return -1;
-  if (!equal) return gf2_bad_arg(fn, "equal is null");
+  GF2_RC(gf2_refuse_null(fn, "equal", equal));
   if (A->nrows != B->nrows || A->ncols != B->ncols) {
     *equal = 0;
     return 0;

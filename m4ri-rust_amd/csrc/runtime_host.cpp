@@ -365,7 +365,7 @@ size_t gf2_dev_arena_limit(hipStream_t s) {
   (void)hipGetDevice(&dev);
   {
     std::lock_guard<std::mutex> lk(g_ws_mu);
-    auto it = g_ws.find(std::make_tuple(dev, s, 0));
+    auto it = g_ws.find(std::make_tuple(dev, s, (int)GF2_SLOT_OPERANDS));
     if (it != g_ws.end()) mine += it->second.bytes;
   }
   {

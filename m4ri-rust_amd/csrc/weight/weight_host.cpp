@@ -8,46 +8,24 @@
 #include <string>
 
 #include "../../../include/m4ri_hip_weight.h"
-#include "../api_internal.h"
+#include "../dev_args.h"
 #include "gf2_weight.h"
 #include "weight_plan.h"
 
 namespace {
-
-// scratch slots (api_internal.h lists 0 .. 7)
-constexpr int kSlotColPartials = 8, kSlotSelectCounts = 9;
-
-bool ranges_meet(const void *p, long long pbytes, const void *q, long long qbytes) {
-  const __int128 a0 = reinterpret_cast<uintptr_t>(p), a1 = a0 + pbytes;
-  const __int128 b0 = reinterpret_cast<uintptr_t>(q), b1 = b0 + qbytes;
-  return pbytes > 0 && qbytes > 0 && a0 < b1 && b0 < a1;
-}
-
-// do the `bytes` bytes at p meet the address range of M's words?
-bool range_meets_mat(const void *p, long long bytes, gf2_dmat const *M) {
-  if (M->nrows <= 0 || M->ncols <= 0 || bytes <= 0) return false;
-  const __int128 a0 = reinterpret_cast<uintptr_t>(p), a1 = a0 + bytes;
-  const __int128 m0 = reinterpret_cast<uintptr_t>(M->data);
-  const __int128 m1 = m0 + 8 * ((__int128)(M->nrows - 1) * M->ld + (((long long)M->ncols + 63) >> 6));
-  return a0 < m1 && m0 < a1;
-}
 
 // 0: go ahead; 1: nothing to do; -1: refused (gf2_last_error is set).  `out` holds `count` elements of `size` bytes
 int check_call(const char *fn, gf2_dmat const *A, const char *name, const void *out, long long count, int size) {
   if (gf2_check_mat(fn, "A", A)) return -1;
   if (count == 0) return 1;
   const std::string n(name);
-  if (!out) return gf2_bad_arg(fn, n + " is null");
-  if (reinterpret_cast<uintptr_t>(out) & (size - 1)) return gf2_bad_arg(fn, n + " is not " + std::to_string(size) + "-byte aligned");
-  if (range_meets_mat(out, count * size, A))
+  GF2_RC(gf2_check_ptr(fn, n, out, size));
+  if (gf2_range_meets_mat(out, count * size, A))
     return gf2_bad_arg(fn, n + " and A overlap: the address range of " + n + " may not meet A's");
   return 0;
 }
 
-int clear_async(const char *fn, void *p, size_t bytes, hipStream_t s) {
-  const hipError_t e = hipMemsetAsync(p, 0, bytes, s);
-  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
-}
+int clear_async(const char *fn, void *p, size_t bytes, hipStream_t s) { return gf2_hip_rc(hipMemsetAsync(p, 0, bytes, s), fn); }
 
 }  // namespace
 
@@ -58,7 +36,7 @@ extern "C" int gf2_row_weights_dev(gf2_dmat const *A, int *weights, void *stream
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (A->ncols == 0) return clear_async(fn, weights, 4 * (size_t)A->nrows, s);
   const hipError_t e = gf2k_weight_rows(A->data, A->ld, A->nrows, A->ncols, weights, s);
-  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+  return gf2_hip_rc(e, fn);
 }
 
 extern "C" int gf2_col_weights_dev(gf2_dmat const *A, int *weights, void *stream) {
@@ -70,13 +48,13 @@ extern "C" int gf2_col_weights_dev(gf2_dmat const *A, int *weights, void *stream
   const WeightColsPlan plan = weight_cols_plan(A->nrows, A->ncols);
   if (plan.scratch == 0) {
     const hipError_t e = gf2k_weight_cols(A->data, A->ld, A->nrows, A->ncols, weights, nullptr, s);
-    return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+    return gf2_hip_rc(e, fn);
   }
   std::lock_guard<std::mutex> lk(gf2_enqueue_mu);  // another thread on the same stream would be handed the same scratch
   void *partial = nullptr;
-  GF2_RC(gf2_stream_scratch(s, (size_t)plan.scratch, &partial, kSlotColPartials));
+  GF2_RC(gf2_stream_scratch(s, (size_t)plan.scratch, &partial, GF2_SLOT_WEIGHT_COL_PARTIALS));
   const hipError_t e = gf2k_weight_cols(A->data, A->ld, A->nrows, A->ncols, weights, static_cast<int *>(partial), s);
-  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+  return gf2_hip_rc(e, fn);
 }
 
 extern "C" int gf2_count_ones_dev(gf2_dmat const *A, unsigned long long *total, void *stream) {
@@ -86,33 +64,33 @@ extern "C" int gf2_count_ones_dev(gf2_dmat const *A, unsigned long long *total, 
   hipStream_t s = static_cast<hipStream_t>(stream);
   GF2_RC(clear_async(fn, total, 8, s));  // the workgroups add into it behind this, on the same stream
   const hipError_t e = gf2k_weight_total(A->data, A->ld, A->nrows, A->ncols, total, s);
-  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+  return gf2_hip_rc(e, fn);
 }
 
 extern "C" int gf2_select_weights_dev(const int *weights, int n, int lo, int hi, int *idx, int cap, int *count, void *stream) {
   static const char fn[] = "gf2_select_weights_dev";
   if (n < 0) return gf2_bad_arg(fn, "n is negative");
   if (cap < 0) return gf2_bad_arg(fn, "cap is negative");
-  if (n > 0 && !weights) return gf2_bad_arg(fn, "weights is null");
-  if (!count) return gf2_bad_arg(fn, "count is null");
-  if (cap > 0 && !idx) return gf2_bad_arg(fn, "idx is null");
-  if (reinterpret_cast<uintptr_t>(weights) & 3) return gf2_bad_arg(fn, "weights is not 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(idx) & 3) return gf2_bad_arg(fn, "idx is not 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(count) & 3) return gf2_bad_arg(fn, "count is not 4-byte aligned");
+  if (n > 0) GF2_RC(gf2_refuse_null(fn, "weights", weights));
+  GF2_RC(gf2_refuse_null(fn, "count", count));
+  if (cap > 0) GF2_RC(gf2_refuse_null(fn, "idx", idx));
+  GF2_RC(gf2_refuse_misaligned(fn, "weights", weights, 4));
+  GF2_RC(gf2_refuse_misaligned(fn, "idx", idx, 4));
+  GF2_RC(gf2_refuse_misaligned(fn, "count", count, 4));
   if (n == 0 && cap == 0) return 0;
-  if (idx && ranges_meet(idx, 4ll * cap, weights, 4ll * n))
+  if (idx && gf2_ranges_meet(idx, 4ll * cap, weights, 4ll * n))
     return gf2_bad_arg(fn, "idx and weights overlap: the address range of idx may not meet that of weights");
-  if (ranges_meet(count, 4, weights, 4ll * n)) return gf2_bad_arg(fn, "count and weights overlap: count may not lie inside weights");
-  if (idx && ranges_meet(count, 4, idx, 4ll * cap)) return gf2_bad_arg(fn, "count and idx overlap: count may not lie inside idx");
+  if (gf2_ranges_meet(count, 4, weights, 4ll * n)) return gf2_bad_arg(fn, "count and weights overlap: count may not lie inside weights");
+  if (idx && gf2_ranges_meet(count, 4, idx, 4ll * cap)) return gf2_bad_arg(fn, "count and idx overlap: count may not lie inside idx");
   GF2_RC(gf2_require_device());
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (n == 0) return clear_async(fn, count, 4, s);
   std::lock_guard<std::mutex> lk(gf2_enqueue_mu);  // another thread on the same stream would be handed the same scratch
   const long long nblk = ((long long)n + kWeightSelectBlock - 1) / kWeightSelectBlock;
   void *counts = nullptr;
-  GF2_RC(gf2_stream_scratch(s, (size_t)(4 * nblk), &counts, kSlotSelectCounts));
+  GF2_RC(gf2_stream_scratch(s, (size_t)(4 * nblk), &counts, GF2_SLOT_WEIGHT_SELECT_COUNTS));
   const hipError_t e = gf2k_weight_select(weights, n, lo, hi, idx, cap, count, static_cast<int *>(counts), s);
-  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+  return gf2_hip_rc(e, fn);
 }
 
 extern "C" int gf2_weights_plan(int what, int nrows, int ncols, long long out[4]) {

@@ -8,28 +8,11 @@
 #include <string>
 
 #include "../../../include/m4ri_hip_wht.h"
-#include "../api_internal.h"
+#include "../dev_args.h"
 #include "gf2_wht.h"
 #include "wht_plan.h"
 
 namespace {
-
-constexpr int kSlotMinPartials = 10;  // scratch slot (api_internal.h lists 0 .. 9)
-
-bool ranges_meet(const void *p, long long pbytes, const void *q, long long qbytes) {
-  const __int128 a0 = reinterpret_cast<uintptr_t>(p), a1 = a0 + pbytes;
-  const __int128 b0 = reinterpret_cast<uintptr_t>(q), b1 = b0 + qbytes;
-  return pbytes > 0 && qbytes > 0 && a0 < b1 && b0 < a1;
-}
-
-// do the `bytes` bytes at p meet the address range of M's words?
-bool range_meets_mat(const void *p, long long bytes, gf2_dmat const *M) {
-  if (M->nrows <= 0 || M->ncols <= 0 || bytes <= 0) return false;
-  const __int128 a0 = reinterpret_cast<uintptr_t>(p), a1 = a0 + bytes;
-  const __int128 m0 = reinterpret_cast<uintptr_t>(M->data);
-  const __int128 m1 = m0 + 8 * ((__int128)(M->nrows - 1) * M->ld + (((long long)M->ncols + 63) >> 6));
-  return a0 < m1 && m0 < a1;
-}
 
 int check_k(const char *fn, int k) {
   if (k < 0 || k > kWhtMaxK) return gf2_bad_arg(fn, "k = " + std::to_string(k) + " is outside 0 <= k <= " + std::to_string(kWhtMaxK));
@@ -39,8 +22,7 @@ int check_k(const char *fn, int k) {
 // an array of 2^k ints; align16: the transform runs over it
 int check_array(const char *fn, const char *name, const void *p, int k, bool align16) {
   const std::string n(name);
-  if (!p) return gf2_bad_arg(fn, n + " is null");
-  if (reinterpret_cast<uintptr_t>(p) & 3) return gf2_bad_arg(fn, n + " is not 4-byte aligned");
+  GF2_RC(gf2_check_ptr(fn, n, p, 4));
   if (align16 && k >= 2 && (reinterpret_cast<uintptr_t>(p) & 15))
     return gf2_bad_arg(fn, n + " is not 16-byte aligned (the transform of 4 or more elements moves 16 bytes per access)");
   return 0;
@@ -58,17 +40,15 @@ int check_tally(const char *fn, gf2_dmat const *P, int c0, int k, int label_col,
     return gf2_bad_arg(fn, "label_col = " + std::to_string(label_col) + " is outside P (" + std::to_string(P->ncols) + " columns" +
                                (min_label < 0 ? "; -1: no label)" : "; a label is required)"));
   GF2_RC(check_array(fn, name, out, k, align16));
-  if (range_meets_mat(out, 4ll << k, P))
+  if (gf2_range_meets_mat(out, 4ll << k, P))
     return gf2_bad_arg(fn, std::string(name) + " and P overlap: the address range of " + name + " may not meet P's");
   return 0;
 }
 
 int enqueue_tally(const char *fn, gf2_dmat const *P, int c0, int k, int label_col, int *f, hipStream_t s) {
-  hipError_t e = hipMemsetAsync(f, 0, (size_t)4 << k, s);  // the workgroups add into it behind this, on the same stream
-  if (e != hipSuccess) return gf2_fail_hip(e, fn);
+  GF2_RC(gf2_hip_rc(hipMemsetAsync(f, 0, (size_t)4 << k, s), fn));  // the workgroups add into it behind this, on the same stream
   if (P->nrows == 0) return 0;
-  e = gf2k_wht_tally(P->data, P->ld, P->nrows, c0, k, label_col, reinterpret_cast<unsigned *>(f), s);
-  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+  return gf2_hip_rc(gf2k_wht_tally(P->data, P->ld, P->nrows, c0, k, label_col, reinterpret_cast<unsigned *>(f), s), fn);
 }
 
 }  // namespace
@@ -87,7 +67,7 @@ extern "C" int gf2_wht_dev(int *f, int k, void *stream) {
   if (k == 0) return 0;  // the identity
   GF2_RC(gf2_require_device());
   const hipError_t e = gf2k_wht_transform(reinterpret_cast<unsigned *>(f), k, 0, 0u, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+  return gf2_hip_rc(e, fn);
 }
 
 extern "C" int gf2_lpn_errors_dev(gf2_dmat const *P, int c0, int k, int label_col, int *errors, void *stream) {
@@ -95,35 +75,32 @@ extern "C" int gf2_lpn_errors_dev(gf2_dmat const *P, int c0, int k, int label_co
   GF2_RC(check_tally(fn, P, c0, k, label_col, 0, "errors", errors, true));
   GF2_RC(gf2_require_device());
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (P->nrows == 0) {  // nobody is wrong about no sample
-    const hipError_t e = hipMemsetAsync(errors, 0, (size_t)4 << k, s);
-    return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
-  }
+  if (P->nrows == 0) return gf2_hip_rc(hipMemsetAsync(errors, 0, (size_t)4 << k, s), fn);  // nobody is wrong about no sample
   GF2_RC(enqueue_tally(fn, P, c0, k, label_col, errors, s));
   // the last pass stores (N - F) / 2; with k == 0 that is all the transform does
   const hipError_t e = gf2k_wht_transform(reinterpret_cast<unsigned *>(errors), k, 1, (unsigned)P->nrows, s);
-  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+  return gf2_hip_rc(e, fn);
 }
 
 extern "C" int gf2_min_weight_dev(const int *w, int n, int *idx, int *val, void *stream) {
   static const char fn[] = "gf2_min_weight_dev";
   if (n < 1) return gf2_bad_arg(fn, "n = " + std::to_string(n) + " is below 1");
-  if (!w) return gf2_bad_arg(fn, "w is null");
-  if (!idx) return gf2_bad_arg(fn, "idx is null");
-  if (!val) return gf2_bad_arg(fn, "val is null");
-  if (reinterpret_cast<uintptr_t>(w) & 3) return gf2_bad_arg(fn, "w is not 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(idx) & 3) return gf2_bad_arg(fn, "idx is not 4-byte aligned");
-  if (reinterpret_cast<uintptr_t>(val) & 3) return gf2_bad_arg(fn, "val is not 4-byte aligned");
-  if (ranges_meet(idx, 4, w, 4ll * n)) return gf2_bad_arg(fn, "idx and w overlap: idx may not lie inside w");
-  if (ranges_meet(val, 4, w, 4ll * n)) return gf2_bad_arg(fn, "val and w overlap: val may not lie inside w");
-  if (ranges_meet(idx, 4, val, 4)) return gf2_bad_arg(fn, "idx and val overlap");
+  GF2_RC(gf2_refuse_null(fn, "w", w));
+  GF2_RC(gf2_refuse_null(fn, "idx", idx));
+  GF2_RC(gf2_refuse_null(fn, "val", val));
+  GF2_RC(gf2_refuse_misaligned(fn, "w", w, 4));
+  GF2_RC(gf2_refuse_misaligned(fn, "idx", idx, 4));
+  GF2_RC(gf2_refuse_misaligned(fn, "val", val, 4));
+  if (gf2_ranges_meet(idx, 4, w, 4ll * n)) return gf2_bad_arg(fn, "idx and w overlap: idx may not lie inside w");
+  if (gf2_ranges_meet(val, 4, w, 4ll * n)) return gf2_bad_arg(fn, "val and w overlap: val may not lie inside w");
+  if (gf2_ranges_meet(idx, 4, val, 4)) return gf2_bad_arg(fn, "idx and val overlap");
   GF2_RC(gf2_require_device());
   hipStream_t s = static_cast<hipStream_t>(stream);
   std::lock_guard<std::mutex> lk(gf2_enqueue_mu);  // another thread on the same stream would be handed the same scratch
   void *partial = nullptr;
-  GF2_RC(gf2_stream_scratch(s, (size_t)wht_min_scratch(n), &partial, kSlotMinPartials));
+  GF2_RC(gf2_stream_scratch(s, (size_t)wht_min_scratch(n), &partial, GF2_SLOT_WHT_MIN_PARTIALS));
   const hipError_t e = gf2k_wht_min(w, n, idx, val, static_cast<int *>(partial), s);
-  return e == hipSuccess ? 0 : gf2_fail_hip(e, fn);
+  return gf2_hip_rc(e, fn);
 }
 
 extern "C" int gf2_wht_plan(int k, long long out[12]) {

@@ -6,7 +6,8 @@
 // Every case runs on a plain matrix and on a window at (3, 64) of a dirty parent whose columns do not end on a word.  Every result is
 // compared bit for bit with the oracle or with a plain loop written here, and the parent -- for a plain matrix: the excess bits of the
 // last word and the padding words of the row stride -- is compared bit by bit outside the operand.  Leak detection is on: a matrix that
-// a routine forgets to free fails the run.  argv[1]: a directory for the file of the save / load round trip.
+// a routine forgets to free fails the run.  The overlap predicates of dev_args.h are pure arithmetic and run here too, against
+// enumerated bits and bytes.  argv[1]: a directory for the file of the save / load round trip.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -15,7 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "api_internal.h"
+#include "dev_args.h"
 #include "gf2_oracle.h"
 
 extern int g_stub_devices, g_stub_device_calls, g_stub_pin_requests;
@@ -581,11 +582,95 @@ static void run_pinned_fallback() {
   report("pinned pool fallback", 1);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// the aliasing predicates of dev_args.h, which every device-resident entry relies on, against enumerated sets of bits and bytes.  The
+// addresses are numbers: nothing is read through them.
+// ---------------------------------------------------------------------------------------------------------------------------------
+static void run_arg_rules() {
+  long n = 0;
+  const long long BASE = 1ll << 20;  // a bit address for the rectangles, a byte address for the ranges
+  static unsigned char in_x[4096];
+  const int COLS[] = {1, 63, 64, 65, 128, 130};
+  // rectangles of bits: X at BASE + 37 (its first bit lies inside a word), Y at every distance at which the two can meet, and beyond
+  for (int ldx = 1; ldx <= 3; ++ldx) for (int ldy = 1; ldy <= 3; ++ldy) for (int xr = 1; xr <= 3; ++xr) for (int xc : COLS) {
+    if (xc > 64 * ldx) continue;
+    const int reach_x = (xr - 1) * 64 * ldx + xc;  // bits from the first to one past the last
+    memset(in_x, 0, sizeof in_x);
+    for (int i = 0; i < xr; ++i)
+      for (int j = 0; j < xc; ++j) in_x[1024 + i * 64 * ldx + j] = 1;
+    for (int yr = 1; yr <= 3; ++yr) for (int yc : COLS) {
+      if (yc > 64 * ldy) continue;
+      const int reach_y = (yr - 1) * 64 * ldy + yc;
+      if (reach_x + 70 > 1024 || reach_y + 70 > 1024) FAIL("arg rules driver: the window is too small");
+      // with one stride every distance; with two, where the answer may be anything but "no" is required, every 5th
+      for (int d = -(reach_y + 69); d <= reach_x + 69; d += ldx == ldy ? 1 : 5) {
+        bool share = false;
+        for (int i = 0; i < yr && !share; ++i)
+          for (int j = 0; j < yc && !share; ++j) share = in_x[1024 + d + i * 64 * ldy + j];
+        const bool got = gf2_bit_rects_share((__int128)BASE + 37, ldx, xr, xc, (__int128)BASE + 37 + d, ldy, yr, yc);
+        if (ldx == ldy ? got != share : share && !got)
+          FAIL("gf2_bit_rects_share: ld %d / %d, %d x %d and %d x %d at distance %d: %d, the bits say %d", ldx, ldy, xr, xc, yr, yc, d, got, share);
+        ++n;
+      }
+    }
+  }
+  // byte ranges: flat against flat
+  auto ptr = [&](long long byte) { return reinterpret_cast<const void *>(static_cast<uintptr_t>(BASE + byte)); };
+  for (int a = 0; a < 24; ++a) for (int la : {0, 1, 2, 5, 12}) for (int b = 0; b < 24; ++b) for (int lb : {0, 1, 2, 5, 12}) {
+    bool share = false;
+    for (int x = a; x < a + la; ++x) share |= x >= b && x < b + lb;
+    if (gf2_ranges_meet(ptr(a), la, ptr(b), lb) != share) FAIL("gf2_ranges_meet: [%d, +%d) and [%d, +%d)", a, la, b, lb);
+    ++n;
+  }
+  // a matrix's range: every byte from the first of its words to the last, the padding of the rows in between included
+  typedef std::vector<char> Bytes;  // of a window of 160 bytes at BASE
+  auto bytes_of = [&](const gf2_dmat &M) {
+    Bytes s(160, 0);
+    int lo = 160, hi = 0;
+    for (int i = 0; i < M.nrows; ++i)
+      for (int w = 0; w < wordsof(M.ncols); ++w) {
+        const int at = (int)(reinterpret_cast<uintptr_t>(M.data) - BASE) + 8 * (i * (int)M.ld + w);
+        lo = std::min(lo, at), hi = std::max(hi, at + 8);
+      }
+    for (int x = lo; x < hi; ++x) s[x] = 1;
+    return s;
+  };
+  std::vector<gf2_dmat> mats;
+  for (int at : {0, 8, 24}) for (int r = 0; r <= 3; ++r) for (int c : {0, 1, 64, 65}) for (int pad = 0; pad < 2; ++pad) {
+    gf2_dmat M{};
+    M.data = reinterpret_cast<uint64_t *>(static_cast<uintptr_t>(BASE + 40 + at));
+    M.nrows = r, M.ncols = c, M.ld = std::max(1, wordsof(c)) + pad;
+    mats.push_back(M);
+  }
+  for (const gf2_dmat &M : mats) {
+    const Bytes m = bytes_of(M);
+    const int m0 = (int)(reinterpret_cast<uintptr_t>(M.data) - BASE);
+    for (int a = 0; a < 150; ++a) for (int la : {0, 1, 4, 9}) {
+      bool share = false;
+      for (int x = a; x < a + la; ++x) share |= m[x] != 0;
+      if (gf2_range_meets_mat(ptr(a), la, &M) != share)
+        FAIL("gf2_range_meets_mat: [%d, +%d) and a %d x %d matrix at %d, ld %d", a, la, M.nrows, M.ncols, m0, (int)M.ld);
+      ++n;
+    }
+    for (const gf2_dmat &Y : mats) {
+      const Bytes y = bytes_of(Y);
+      bool share = false;
+      for (int x = 0; x < 160; ++x) share |= m[x] && y[x];
+      if (gf2_mat_ranges_meet(&M, &Y) != share)
+        FAIL("gf2_mat_ranges_meet: %d x %d at %d, ld %d, and %d x %d at %d, ld %d", M.nrows, M.ncols, m0, (int)M.ld, Y.nrows, Y.ncols,
+             (int)(reinterpret_cast<uintptr_t>(Y.data) - BASE), (int)Y.ld);
+      ++n;
+    }
+  }
+  report("dev_args.h overlap predicates", n);
+}
+
 int main(int argc, char **argv) {
   if (argc < 2) {
     printf("usage: host_san <scratch directory>\n");
     return 2;
   }
+  run_arg_rules();
   run_echelonize();
   run_ple();
   run_trsm();

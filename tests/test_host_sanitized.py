@@ -3,7 +3,8 @@ leak and undefined-behaviour sanitizers, as a stand-alone program (tests/cpp/hos
 linked with the C oracle as the reference).  These routines run in the caller's process, on its heap through rows[] and on windows of
 its matrices; the other host tests reach them through ctypes, where no sanitizer watches.  Every gf2_*_host_small entry and every
 container function runs over 11 x 11 shapes around the word boundaries, on plain matrices and on windows of dirty parents; results are
-compared bit for bit, the parents bit by bit outside the window.  No device is needed and none is used."""
+compared bit for bit, the parents bit by bit outside the window.  The overlap predicates of csrc/dev_args.h, which every device-resident
+entry relies on, are checked in the same program against enumerated sets of bits and bytes.  No device is needed and none is used."""
 import os
 import re
 import subprocess
@@ -44,6 +45,7 @@ CASES = {
     "mzd_apply_p / mzp": 1936,
     "gf2_mzd_save / gf2_mzd_load": 242,
     "pinned pool fallback": 1,
+    "dev_args.h overlap predicates": 567630,
 }
 
 
