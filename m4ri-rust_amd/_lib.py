@@ -208,6 +208,15 @@ _WHT_PROTOS = {
 }
 WHT_SYMBOLS = tuple(_WHT_PROTOS)
 
+# ... and include/m4ri_hip_bkw.h (tests/test_bkw_contract.py)
+LF1_KEEP_ZERO = 1
+_BKW_PROTOS = {
+    "gf2_class_first_dev": (_I, [DMatP, _I, _I, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_lf1_reduce_dev": (_I, [DMatP, DMatP, _I, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_lf1_plan": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
+}
+BKW_SYMBOLS = tuple(_BKW_PROTOS)
+
 _lib = None
 
 
@@ -220,7 +229,8 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C m4ri-rust_amd/csrc`). There is no fallback for the HIP multiply path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in list(_PROTOS.items()) + list(_GATHER_PROTOS.items()) + list(_WEIGHT_PROTOS.items()) + list(_WHT_PROTOS.items()):
+        tables = (_PROTOS, _GATHER_PROTOS, _WEIGHT_PROTOS, _WHT_PROTOS, _BKW_PROTOS)
+        for name, (res, args) in [item for table in tables for item in table.items()]:
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -54,6 +54,7 @@ enum Gf2ScratchSlot {
   GF2_SLOT_WEIGHT_COL_PARTIALS = 8,    // weight/weight_host.cpp: per-band column sums
   GF2_SLOT_WEIGHT_SELECT_COUNTS = 9,   // weight/weight_host.cpp: block counts of the selection
   GF2_SLOT_WHT_MIN_PARTIALS = 10,      // wht/wht_host.cpp: the per-workgroup minima of gf2_min_weight_dev
+  GF2_SLOT_BKW_BLOCK_COUNTS = 11,      // bkw/bkw_host.cpp: block counts of the compaction of gf2_lf1_reduce_dev
 };
 int gf2_stream_scratch(hipStream_t s, size_t bytes, void **out, int slot);  // slot: a Gf2ScratchSlot
 // counts a run of a host routine of the size dispatch (gf2_host_small_calls)

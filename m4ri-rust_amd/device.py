@@ -166,6 +166,12 @@ class DMat:
         tally, Walsh-Hadamard transform, (N - F) / 2 on the device (include/m4ri_hip_wht.h)."""
         return lpn_errors(self, c0, k, label_col)
 
+    def lf1_reduce(self, c0, b, keep_zero=False):
+        """One LF1 round of a BKW reduction as a new DMat of exactly the surviving rows: every row but the first of its class (classes
+        by the bits [c0, c0 + b)), XORed with that first row, in the order they had (include/m4ri_hip_bkw.h).  keep_zero: the rows
+        whose window is zero already all stay, unchanged."""
+        return lf1_reduce(self, c0, b, keep_zero=keep_zero, src=SKIP)[0]
+
     def set_window(self, start_row, start_col, other):
         """Overwrite the block of other's shape at (start_row, start_col) with other."""
         copy_block(self, start_row, start_col, other, 0, 0, other.nrows, other.ncols)
@@ -527,6 +533,54 @@ def min_weight(w, n, idx=None, val=None, stream=None):
     rc = _lib.lib().gf2_min_weight_dev(wptr, n, own_i.ptr if own_i else idx, own_v.ptr if own_v else val, stream)
     _lib.check(rc, "gf2_min_weight_dev")
     return (int(own_i.read(stream)[0]) if own_i else None), (int(own_v.read(stream)[0]) if own_v else None)
+
+
+def lf1_plan(nrows, ncols, b):
+    """How an LF1 round over nrows x ncols with a window of b bits runs (no device needed) -> (variant of the class-first kernel (0:
+    table in LDS, 1: global atomics), its threads per workgroup, its LDS bytes, rows a workgroup of the count / scatter kernels covers,
+    lanes per row of the scatter kernel, scratch bytes); None for a bad shape."""
+    out = (ctypes.c_longlong * 5)()
+    v = _lib.lib().gf2_lf1_plan(nrows, ncols, b, out)
+    return None if v < 0 else (v, out[0], out[1], out[2], out[3], out[4])
+
+
+def class_first(P, c0, b, out=None, stream=None):
+    """first[v] = the lowest row of P whose bits [c0, c0 + b) read v, -1 where no row does, v < 2^b.  `out` is a raw device address of
+    2^b int32: the call only enqueues on `stream` and None is returned; or None: the wrapper allocates scratch, WAITS for `stream` and
+    returns a numpy int32 array."""
+    L = _lib.lib()
+    return _wht_array("gf2_class_first_dev", lambda p: L.gf2_class_first_dev(P._on(stream), c0, b, p, stream), 1 << b, out, stream)
+
+
+def lf1_reduce(P, c0, b, keep_zero=False, D=None, cap=None, first=None, count=None, src=None, stream=None):
+    """One LF1 round of a BKW reduction (include/m4ri_hip_bkw.h): the rows of P are partitioned by their bits [c0, c0 + b), the first
+    row of every class is XORed into the other rows of its class and dropped; with keep_zero the rows of key 0 stay as they are.
+    -> (D, count, first, src), all on the device: D holds the survivors in their order (D.nrows is the capacity; `count` says how many
+    there are in all), first[v] the first row of class v (2^b int32), src[j] the row of P that D[j] came from.  Each of `first`,
+    `count` and `src` is a raw device address -- the kernels write there, None is returned in its place -- or None: the wrapper
+    allocates the array and returns it as an object with .ptr (its address, which feeds gather_rows / select_weights as it is) and
+    .read(stream) (numpy, waits).  src=SKIP (0): not wanted.  The capacity is D.nrows, else `cap`; the call then only enqueues on
+    `stream`.  With neither (cap=None), a count-only call comes first, the wrapper WAITS for it and sizes D to exactly count rows."""
+    L = _lib.lib()
+    flags = _lib.LF1_KEEP_ZERO if keep_zero else 0
+    own_f = _IntScratch(1 << b) if first is None else None
+    own_c = _IntScratch(1) if count is None else None
+    fptr, cptr = own_f.ptr if own_f else first, own_c.ptr if own_c else count
+    if D is None:
+        if cap is None:
+            if own_c is None:
+                raise ValueError("lf1_reduce: a raw count address needs D or cap (the wrapper cannot read the count to size D)")
+            none = DMat.wrap(None, 0, P.ncols, P.ld)
+            _lib.check(L.gf2_lf1_reduce_dev(none._on(stream), P._on(stream), c0, b, flags, fptr, cptr, None, stream), "gf2_lf1_reduce_dev")
+            cap = int(own_c.read(stream)[0])
+        D = DMat(cap, P.ncols)
+    own_s = _IntScratch(D.nrows) if src is None and D.nrows > 0 else None
+    sptr = own_s.ptr if own_s else (src or None)
+    _lib.check(L.gf2_lf1_reduce_dev(D._on(stream), P._on(stream), c0, b, flags, fptr, cptr, sptr, stream), "gf2_lf1_reduce_dev")
+    for own in (own_f, own_c, own_s):
+        if own:
+            own.mat._streams.add(stream)
+    return D, own_c, own_f, own_s
 
 
 def nullspace(A, stream=None):
