@@ -217,6 +217,27 @@ _BKW_PROTOS = {
 }
 BKW_SYMBOLS = tuple(_BKW_PROTOS)
 
+# ... and include/m4ri_hip_cover.h (tests/test_cover_contract.py)
+COVER_MAX_N, COVER_MAX_R, COVER_MAX_CODES, COVER_MAX_SEGS, COVER_MAX_LEADERS = 32, 12, 16, 256, 16384
+COVER_IDENTITY, COVER_DROP, COVER_REPETITION, COVER_HAMMING, COVER_GOLAY23 = range(5)
+
+
+class CoverCodeStruct(ctypes.Structure):
+    """gf2_cover_code (include/m4ri_hip_cover.h), 56 bytes."""
+    _fields_ = [("n", ctypes.c_int), ("k", ctypes.c_int), ("h", ctypes.c_uint32 * COVER_MAX_R)]
+
+
+assert ctypes.sizeof(CoverCodeStruct) == 56
+
+CoverCodeP = ctypes.POINTER(CoverCodeStruct)
+_COVER_PROTOS = {
+    "gf2_cover_code_named": (_I, [_I, _I, CoverCodeP]),
+    "gf2_cover_leaders": (_I, [CoverCodeP, ctypes.c_void_p, ctypes.POINTER(_I)]),
+    "gf2_cover_reduce_dev": (_I, [DMatP, DMatP, _I, CoverCodeP, _I, ctypes.c_void_p, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_cover_plan": (_I, [_I, _I, CoverCodeP, _I, ctypes.c_void_p, _I, ctypes.POINTER(ctypes.c_longlong)]),
+}
+COVER_SYMBOLS = tuple(_COVER_PROTOS)
+
 _lib = None
 
 
@@ -229,7 +250,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C m4ri-rust_amd/csrc`). There is no fallback for the HIP multiply path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        tables = (_PROTOS, _GATHER_PROTOS, _WEIGHT_PROTOS, _WHT_PROTOS, _BKW_PROTOS)
+        tables = (_PROTOS, _GATHER_PROTOS, _WEIGHT_PROTOS, _WHT_PROTOS, _BKW_PROTOS, _COVER_PROTOS)
         for name, (res, args) in [item for table in tables for item in table.items()]:
             fn = getattr(handle, name)
             fn.restype = res

@@ -172,6 +172,11 @@ class DMat:
         whose window is zero already all stay, unchanged."""
         return lf1_reduce(self, c0, b, keep_zero=keep_zero, src=SKIP)[0]
 
+    def cover_reduce(self, c0, segments):
+        """The covering-code reduction as a new DMat: the columns from c0 on are cut into blocks as long as the codes of `segments` (a
+        list of CoverCode), every block is decoded to its nearest codeword and replaced by the message (include/m4ri_hip_cover.h)."""
+        return cover_reduce(self, c0, segments, dist=SKIP)[0]
+
     def set_window(self, start_row, start_col, other):
         """Overwrite the block of other's shape at (start_row, start_col) with other."""
         copy_block(self, start_row, start_col, other, 0, 0, other.nrows, other.ncols)
@@ -581,6 +586,161 @@ def lf1_reduce(P, c0, b, keep_zero=False, D=None, cap=None, first=None, count=No
         if own:
             own.mat._streams.add(stream)
     return D, own_c, own_f, own_s
+
+
+class CoverCode:
+    """A small [n, k] code in systematic form for cover_reduce() (include/m4ri_hip_cover.h): bit t of a block's syndrome is
+    parity(block & h[t]), and h[t] >> k == 1 << t.  Made by identity(n), drop(n), repetition(n), hamming(r), golay23() or
+    from_rows(n, k, h).  Codes compare equal when n, k, the check rows and the table are equal."""
+
+    def __init__(self, n, k, h=(), table=None):
+        self.s = _lib.CoverCodeStruct()
+        self.s.n, self.s.k = n, k
+        for t, row in enumerate(h):
+            self.s.h[t] = row
+        self._table = None if table is None else np.ascontiguousarray(table, dtype=np.uint32)
+        self._leaders = self._radius = self._dev = None
+
+    n = property(lambda self: self.s.n)
+    k = property(lambda self: self.s.k)
+    r = property(lambda self: self.s.n - self.s.k)
+    h = property(lambda self: tuple(int(x) for x in self.s.h))
+    has_table = property(lambda self: 0 < self.s.k < self.s.n)
+
+    @staticmethod
+    def _named(kind, param):
+        code = CoverCode(0, 0)
+        if _lib.lib().gf2_cover_code_named(kind, param, ctypes.byref(code.s)) != 0:
+            raise ValueError("CoverCode: no code of kind %d with parameter %r" % (kind, param))
+        return code
+
+    @staticmethod
+    def identity(n):
+        """[n, n], 1 <= n <= 32: the bits pass through"""
+        return CoverCode._named(_lib.COVER_IDENTITY, n)
+
+    @staticmethod
+    def drop(n):
+        """[n, 0], 1 <= n <= 32: the bits are dropped (and counted in dist)"""
+        return CoverCode._named(_lib.COVER_DROP, n)
+
+    @staticmethod
+    def repetition(n):
+        """[n, 1], 2 <= n <= 13: the majority bit (a tie decodes to the pattern that is smaller as an integer)"""
+        return CoverCode._named(_lib.COVER_REPETITION, n)
+
+    @staticmethod
+    def hamming(r):
+        """[2^r - 1, 2^r - 1 - r], 2 <= r <= 5"""
+        return CoverCode._named(_lib.COVER_HAMMING, r)
+
+    @staticmethod
+    def golay23():
+        """the binary Golay code [23, 12], covering radius 3"""
+        return CoverCode._named(_lib.COVER_GOLAY23, 0)
+
+    @staticmethod
+    def from_rows(n, k, h, table=None):
+        """The code with the check rows h[0 .. n - k).  table: 2^(n-k) uint32 that the device reads INSTEAD of the coset leaders (the
+        tables are taken as they are).  ValueError for a code outside the limits or a non-systematic h."""
+        h = [int(x) for x in h]
+        if len(h) > _lib.COVER_MAX_R or len(h) < (n - k if 0 < k < n else 0):
+            raise ValueError("CoverCode.from_rows: [%d, %d] with %d check rows is outside the limits" % (n, k, len(h)))
+        code = CoverCode(n, k, h, table)
+        if _lib.lib().gf2_cover_plan(0, 0, ctypes.byref(code.s), 1, None, 0, None) < 0:
+            raise ValueError("CoverCode.from_rows: [%d, %d] breaks the rules of include/m4ri_hip_cover.h" % (n, k))
+        if table is not None and (not code.has_table or code._table.shape != (1 << (n - k),)):
+            raise ValueError("CoverCode.from_rows: the table must hold 2^(n-k) words, and only a code with 1 <= k < n has one")
+        return code
+
+    def _key(self):
+        return (self.n, self.k, self.h[:self.r] if self.has_table else (), None if self._table is None else self._table.tobytes())
+
+    def __eq__(self, other):
+        return isinstance(other, CoverCode) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "CoverCode[%d, %d]" % (self.n, self.k)
+
+    def leaders(self):
+        """The coset leaders as a numpy uint32 array: 2^r entries (none for k == 0), leaders[s] = the pattern of lowest weight with
+        syndrome s, among equal weights the smallest integer (gf2_cover_leaders)."""
+        if self._leaders is None:
+            out = np.zeros(0 if self.k == 0 else 1 << self.r, dtype=np.uint32)
+            radius = ctypes.c_int(0)
+            if _lib.lib().gf2_cover_leaders(ctypes.byref(self.s), out.ctypes.data, ctypes.byref(radius)) != 0:
+                raise ValueError("gf2_cover_leaders refused %r" % self)
+            self._leaders, self._radius = out, radius.value
+        return self._leaders
+
+    @property
+    def radius(self):
+        """the largest weight of a coset leader: the covering radius (0 for identity and drop)"""
+        self.leaders()
+        return self._radius
+
+    def table_ptr(self):
+        """Device address of the table that cover_reduce() reads for this code (the coset leaders unless from_rows() was given a
+        table), None for a code without one.  The copy is made once, WAITS for the upload, and is kept with the code."""
+        if not self.has_table:
+            return None
+        if self._dev is None:
+            self._dev = _IntUpload((self.leaders() if self._table is None else self._table).view(np.int32))
+        return self._dev.ptr
+
+
+def _cover_args(segments):
+    """segments (a list of CoverCode) -> (codes, array of gf2_cover_code, seg_code bytes), the codes deduplicated"""
+    codes, index, seg = [], {}, []
+    for code in segments:
+        if code not in index:
+            index[code] = len(codes)
+            codes.append(code)
+        seg.append(index[code])
+    if len(codes) > _lib.COVER_MAX_CODES or len(seg) > _lib.COVER_MAX_SEGS:
+        raise ValueError("cover: %d distinct codes in %d segments: at most %d in %d" % (len(codes), len(seg), _lib.COVER_MAX_CODES,
+                                                                                         _lib.COVER_MAX_SEGS))
+    arr = (_lib.CoverCodeStruct * max(len(codes), 1))()
+    for i, code in enumerate(codes):
+        ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(code.s), ctypes.sizeof(_lib.CoverCodeStruct))
+    return codes, arr, (ctypes.c_ubyte * max(len(seg), 1))(*seg)
+
+
+def cover_plan(nrows, p_ncols, segments):
+    """How a covering-code reduction of nrows x p_ncols by `segments` (a list of CoverCode) runs (no device needed) -> (variant (0: rows
+    read from global memory, 1: window words staged in LDS), threads per workgroup, LDS bytes, rows per workgroup and pass, lanes per
+    row of the copy, K, bits of the window, table words, workgroups); None for a bad argument."""
+    try:
+        codes, arr, seg = _cover_args(segments)
+    except ValueError:
+        return None
+    out = (ctypes.c_longlong * 8)()
+    v = _lib.lib().gf2_cover_plan(nrows, p_ncols, arr, len(codes), seg, len(segments), out)
+    return None if v < 0 else (v,) + tuple(int(x) for x in out)
+
+
+def cover_reduce(P, c0, segments, D=None, dist=None, stream=None):
+    """The covering-code reduction (include/m4ri_hip_cover.h): the columns of P from c0 on are cut into blocks, block j as long as
+    segments[j] (a CoverCode), every block is decoded to the nearest codeword and replaced by its message -> (D, dist): D (default: a
+    new P.nrows x K matrix, K = the sum of the codes' k) holds the messages side by side, dist[i] the number of bits of row i that the
+    decoding flipped or dropped.  `dist` is a raw device address of P.nrows int32 -- the kernel writes there, None is returned in its
+    place -- or SKIP (0): not wanted, or None: the wrapper allocates the array and returns it as an object with .ptr and .read(stream)
+    (numpy, waits).  The call only enqueues on `stream`, except that a code's table is uploaded (and waited for) the first time the code
+    is used: table_ptr() does that ahead of a chain."""
+    codes, arr, seg = _cover_args(segments)
+    tables = (ctypes.c_void_p * max(len(codes), 1))(*[code.table_ptr() for code in codes])
+    if D is None:
+        D = DMat(P.nrows, sum(code.k for code in segments))
+    own = _IntScratch(P.nrows) if dist is None and P.nrows > 0 else None
+    dptr = own.ptr if own else (dist or None)
+    rc = _lib.lib().gf2_cover_reduce_dev(D._on(stream), P._on(stream), c0, arr, len(codes), seg, len(segments), tables, dptr, stream)
+    _lib.check(rc, "gf2_cover_reduce_dev")
+    if own:
+        own.mat._streams.add(stream)
+    return D, own
 
 
 def nullspace(A, stream=None):
