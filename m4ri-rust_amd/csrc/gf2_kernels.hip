@@ -32,7 +32,8 @@
 //    n <= 8 uses an AND/popcount kernel (gf2_narrow_kernel) that streams A at HBM speed; up to 64 vectors against LONG rows
 //    (l > 512: `&A * &v` on a big square A) take gf2_widevec_kernel, a wave per row with lanes along the row, or gf2_tallskinny7_kernel,
 //    4-bit tables rebuilt per 512-bit slab with the inner dimension divided among workgroups (9-64 vectors).
-//  * the Strassen passes fuse three levels (and a virtual fourth) per kernel in registers (gf2_strassen_split3 / merge3_kernel);
+//  * the Strassen passes fuse three levels (and a virtual fourth) per kernel in registers (gf2_strassen_split3 / merge3_kernel; the
+//    four-level merge keeps its 256 sums per position in LDS, strassen/gf2_merge4.inc);
 //    transpose, XOR, compare, fill, padding are HBM-streaming kernels with 16- or 8-byte accesses.  The elimination kernels live in gf2_elim.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -2415,6 +2416,8 @@ __global__ __launch_bounds__(256) void gf2_strassen_merge3_kernel(u64 *__restric
   }
 }
 
+#include "strassen/gf2_merge4.inc"  // gf2_strassen_merge4_kernel: the four levels of a virtual-level step folded into C, sums in LDS
+
 // ---------------------------------------------------------------------------------------------
 // launchers (internal C ABI used by mul_dev_host.cpp and the other host units)
 // ---------------------------------------------------------------------------------------------
@@ -3227,6 +3230,20 @@ extern "C" hipError_t gf2k_strassen_merge3(u64 *dst, long long ldd, long long ds
     hipLaunchKernelGGL(gf2_strassen_merge3_kernel<true>, dim3(gx, groups, batch), dim3(256), 0, stream, dst, ldd, dstStride, src, lds_,
                        srcStride, h, w, accumulate);
   (void)ntl;
+  return hipGetLastError();
+}
+
+// 2401 products per batch element -> C (16h rows x 16w words) in one launch: three fused levels and the virtual one on top
+// (strassen/gf2_merge4.inc).  Element b at dst + b * dstStride, its products at src + b * 2401 * srcStride, group q0 first.
+extern "C" hipError_t gf2k_strassen_merge4(u64 *dst, long long ldd, long long dstStride, const u64 *src, long long lds_,
+                                           long long srcStride, int h, int w, int accumulate, int batch, hipStream_t stream) {
+  if (h <= 0 || w <= 0 || batch <= 0) return hipSuccess;
+  const hipError_t e = lds_limit_once(reinterpret_cast<const void *>(&gf2_strassen_merge4_kernel), kMerge4LdsBytes);
+  if (e != hipSuccess) return e;
+  // one workgroup per CU (its sums fill the LDS): a grid of 256 / batch walks the position blocks in step
+  const int gx = grid_for((long long)h * w, 64, (256 + batch - 1) / batch);
+  hipLaunchKernelGGL(gf2_strassen_merge4_kernel, dim3(gx, batch), dim3(kMerge4Threads), kMerge4LdsBytes, stream, dst, ldd, dstStride,
+                     src, lds_, srcStride, h, w, accumulate);
   return hipGetLastError();
 }
 

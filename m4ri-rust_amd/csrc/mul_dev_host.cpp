@@ -295,9 +295,8 @@ static int mul_strassen(gf2_dmat *C, const gf2_dmat *A, const gf2_dmat *B, int a
       } else if (!st.virt) {
         HIP_TRY(gf2k_strassen_merge3(dst, ldd, strD, Pop[i], wi, dP, mi, wi, acc, 1, batch, s));
       } else {
-        const int m1 = m >> (up + 1), w1 = (n >> (up + 1)) / 64;  // the 7 parents of the virtual level, dense
-        HIP_TRY(gf2k_strassen_merge3(Pop[up + 1], w1, (long long)m1 * w1, Pop[i], wi, dP, mi, wi, 0, 7, batch, s));
-        HIP_TRY(gf2k_strassen_merge(dst, ldd, strD, Pop[up + 1], w1, (long long)m1 * w1, m1, w1, acc, batch, s));
+        // the 7 parents of the virtual level are never written: their sums live in LDS (the arena's slots for them go unused)
+        HIP_TRY(gf2k_strassen_merge4(dst, ldd, strD, Pop[i], wi, dP, mi, wi, acc, batch, s));
       }
       i = up;
     }

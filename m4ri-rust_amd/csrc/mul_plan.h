@@ -65,6 +65,8 @@ std::vector<PlanStep> strassen_plan(int L);
 size_t pow7(int i);
 // The operand arena of an L-level product: word offsets of the operands (a, b) and products (p) of every level at which a plan step
 // ends -- p also for the parents of a virtual level --, and the total.  The workspace query sizes it, mul_strassen carves it.
+// The slots of a virtual level's parents go unused: gf2_strassen_merge4_kernel folds the leaves straight into C and never writes
+// them.  They stay in the arena because the workspace a caller was told to provide is part of the interface.
 struct StrassenArena {  // (L <= 6: pick_levels and plan_product never give more)
   static constexpr size_t none = ~(size_t)0;  // a level the plan does not materialise
   size_t a[7], b[7], p[7], words = 0;

@@ -321,7 +321,7 @@ static double plain_time_model(int m, int l, int n) { return plain_plan(m, l, n)
 // product merges.  The passes fuse levels so that intermediate operands are never written:
 //   step {k, virt}: k (1..3) levels fused in one kernel, operands materialised at the step's end; virt: one more level on
 //   top that is never materialised -- the kernel reads the one or two quadrants of the grandparent whose XOR is its source
-//   (on the product side the 7 parents of that level ARE materialised: merge3 into them, then a single-level merge).
+//   (on the product side the 7 parents of that level are sums in LDS: gf2_strassen_merge4_kernel folds all four levels into C).
 //   L: 1 {1}  2 {2}  3 {3}  4 {3 + virtual}  5 {2, 3}  6 {3, 3}          (M4RI_HIP_STRASSEN_FUSE3=0: pairs only, round 1's plan)
 std::vector<PlanStep> strassen_plan(int L) {
   const int fuse3 = env_int("M4RI_HIP_STRASSEN_FUSE3", 1);  // read per call: the tests switch plans
@@ -387,8 +387,8 @@ static double strassen_pass_bytes(double m, double l, double n, int L) {
     const double a_i = (m * l) / std::pow(4.0, i) / 8.0, b_i = (l * n) / std::pow(4.0, i) / 8.0, c_i = (m * n) / std::pow(4.0, i) / 8.0;
     const double rd = st.virt ? 12.0 * std::pow(4.0, st.k) : std::pow(4.0, st.k), wr = std::pow(7.0, st.levels());
     bytes += p7 * (rd + wr) * (a_i + b_i);  // operand sides
-    if (st.virt)  // products: merge3 into the 7 level-(prev+1) parents, then a single-level merge
-      bytes += p7 * c_i * (wr + 7.0 * std::pow(4.0, st.k) + 7.0 * std::pow(4.0, st.k) + std::pow(4.0, st.k + 1));
+    if (st.virt)  // products: the leaves read once and C written once (gf2_strassen_merge4_kernel keeps the 7 parents in LDS)
+      bytes += p7 * c_i * (wr + std::pow(4.0, st.k + 1));
     else
       bytes += p7 * c_i * (wr + std::pow(4.0, st.k));
     prev = i;
@@ -472,7 +472,7 @@ StrassenArena strassen_arena(int m, int l, int n, int L) {
     ar.words += p7 * li * (ni / 64);
     ar.p[i] = ar.words;
     ar.words += p7 * mi * (ni / 64);
-    if (st.virt) {  // the parents of the virtual level exist on the product side only
+    if (st.virt) {  // the parents of the virtual level: unused since the four-level merge keeps them in LDS (see mul_plan.h)
       ar.p[prev + 1] = ar.words;
       ar.words += pow7(prev + 1) * ((size_t)m >> (prev + 1)) * (((size_t)n >> (prev + 1)) / 64);
     }

@@ -5,7 +5,7 @@ LIB_SRC := gf2_kernels.hip gf2_elim.hip gf2_elim_batch.hip gf2_ple.hip gf2_trsm.
            bkw/gf2_bkw.hip bkw/bkw_host.cpp cover/gf2_cover.hip cover/cover_host.cpp \
            runtime_host.cpp mul_plan_host.cpp mul_dev_host.cpp m4ri_hip_api.cpp elim_host.cpp mzd_host.cpp gf2_small_host.cpp \
            ple_host.cpp trsm_host.cpp nullspace_host.cpp blocks_host.cpp elim_batch_host.cpp
-LIB_HDR := gf2_kernels.h gf2_env.h gf2_variants.h gf2_lpn.inc api_internal.h dev_args.h mul_plan.h gather/gather_plan.h gather/gf2_gather.h \
+LIB_HDR := gf2_kernels.h gf2_env.h gf2_variants.h gf2_lpn.inc strassen/gf2_merge4.inc api_internal.h dev_args.h mul_plan.h gather/gather_plan.h gather/gf2_gather.h \
            weight/weight_plan.h weight/gf2_weight.h wht/wht_plan.h wht/gf2_wht.h bkw/bkw_plan.h bkw/gf2_bkw.h cover/cover_plan.h cover/gf2_cover.h \
            ../../include/m4ri_hip.h ../../include/m4ri_hip_gather.h ../../include/m4ri_hip_weight.h ../../include/m4ri_hip_wht.h \
            ../../include/m4ri_hip_bkw.h ../../include/m4ri_hip_cover.h
