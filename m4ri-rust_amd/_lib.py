@@ -238,6 +238,14 @@ _COVER_PROTOS = {
 }
 COVER_SYMBOLS = tuple(_COVER_PROTOS)
 
+# ... and include/m4ri_hip_lf2.h (tests/test_lf2_contract.py)
+_LF2_PROTOS = {
+    "gf2_class_sort_dev": (_I, [DMatP, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_lf2_reduce_dev": (_I, [DMatP, DMatP, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_lf2_plan": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
+}
+LF2_SYMBOLS = tuple(_LF2_PROTOS)
+
 _lib = None
 
 
@@ -250,7 +258,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C m4ri-rust_amd/csrc`). There is no fallback for the HIP multiply path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        tables = (_PROTOS, _GATHER_PROTOS, _WEIGHT_PROTOS, _WHT_PROTOS, _BKW_PROTOS, _COVER_PROTOS)
+        tables = (_PROTOS, _GATHER_PROTOS, _WEIGHT_PROTOS, _WHT_PROTOS, _BKW_PROTOS, _COVER_PROTOS, _LF2_PROTOS)
         for name, (res, args) in [item for table in tables for item in table.items()]:
             fn = getattr(handle, name)
             fn.restype = res

@@ -172,6 +172,12 @@ class DMat:
         whose window is zero already all stay, unchanged."""
         return lf1_reduce(self, c0, b, keep_zero=keep_zero, src=SKIP)[0]
 
+    def lf2_reduce(self, c0, b):
+        """One LF2 round of a BKW reduction as a new DMat of exactly `count` rows: the XOR of every pair of rows inside a class
+        (classes by the bits [c0, c0 + b)), classes by ascending key, the pairs of a class by (higher row, lower row)
+        (include/m4ri_hip_lf2.h)."""
+        return lf2_reduce(self, c0, b, lo=SKIP, hi=SKIP)[0]
+
     def cover_reduce(self, c0, segments):
         """The covering-code reduction as a new DMat: the columns from c0 on are cut into blocks as long as the codes of `segments` (a
         list of CoverCode), every block is decoded to its nearest codeword and replaced by the message (include/m4ri_hip_cover.h)."""
@@ -586,6 +592,75 @@ def lf1_reduce(P, c0, b, keep_zero=False, D=None, cap=None, first=None, count=No
         if own:
             own.mat._streams.add(stream)
     return D, own_c, own_f, own_s
+
+
+def lf2_plan(nrows, ncols, b):
+    """How the class sort and an LF2 round over nrows x ncols with a window of b bits run (no device needed) -> (sort passes, key bits
+    per pass, threads per workgroup, LDS bytes of the sort kernels, rows per sort tile, rows per run of the pair kernels, lanes per
+    row of the pair scatter, scratch bytes of class_sort, scratch bytes of lf2_reduce); None for a bad shape."""
+    out = (ctypes.c_longlong * 8)()
+    v = _lib.lib().gf2_lf2_plan(nrows, ncols, b, out)
+    return None if v < 0 else (v,) + tuple(int(x) for x in out)
+
+
+class _Int64Scratch(_IntScratch):
+    """one device int64 (the count of lf2_reduce)"""
+
+    def __init__(self):
+        _IntScratch.__init__(self, 2)
+
+    def read(self, stream):
+        return _IntScratch.read(self, stream).view(np.int64)
+
+
+def class_sort(P, c0, b, order=None, skeys=None, stream=None):
+    """The rows of P sorted by their bits [c0, c0 + b), ties in ascending row order (a stable sort; include/m4ri_hip_lf2.h)
+    -> (order, skeys): order[s] the row at sorted position s, skeys[s] its key.  Each is a raw device address of P.nrows int32 -- the
+    kernels write there, the call only enqueues on `stream` and None is returned in its place -- or None: the wrapper allocates the
+    array and returns it as an object with .ptr and .read(stream) (numpy, waits).  skeys=SKIP (0): not wanted."""
+    own_o = _IntScratch(max(P.nrows, 1)) if order is None else None   # an address even where no row is sorted
+    own_k = _IntScratch(max(P.nrows, 1)) if skeys is None else None
+    for own in (own_o, own_k):
+        if own:
+            own.count = P.nrows
+    kptr = own_k.ptr if own_k else (skeys or None)
+    _lib.check(_lib.lib().gf2_class_sort_dev(P._on(stream), c0, b, own_o.ptr if own_o else order, kptr, stream), "gf2_class_sort_dev")
+    for own in (own_o, own_k):
+        if own:
+            own.mat._streams.add(stream)
+    return own_o, own_k
+
+
+def lf2_reduce(P, c0, b, D=None, cap=None, count=None, lo=None, hi=None, stream=None):
+    """One LF2 round of a BKW reduction (include/m4ri_hip_lf2.h): the rows of P are partitioned by their bits [c0, c0 + b) and every
+    pair of rows inside a class is XORed.  -> (D, count, lo, hi), all on the device: D holds the pairs, classes by ascending key and
+    the pairs of a class by (higher row, lower row) (D.nrows is the capacity; `count`, an int64, says how many there are in all),
+    lo[j] < hi[j] the rows of P that D[j] came from.  Each of `count`, `lo` and `hi` is a raw device address -- the kernels write
+    there, None is returned in its place -- or None: the wrapper allocates the array and returns it as an object with .ptr (which
+    feeds gather_rows as it is) and .read(stream) (numpy, waits).  lo / hi = SKIP (0): not wanted.  The capacity is D.nrows, else
+    `cap`; the call then only enqueues on `stream`.  With neither (cap=None), a count-only call comes first, the wrapper WAITS for it
+    and sizes D to exactly count rows."""
+    L = _lib.lib()
+    own_c = _Int64Scratch() if count is None else None
+    cptr = own_c.ptr if own_c else count
+    if D is None:
+        if cap is None:
+            if own_c is None:
+                raise ValueError("lf2_reduce: a raw count address needs D or cap (the wrapper cannot read the count to size D)")
+            none = DMat.wrap(None, 0, P.ncols, P.ld)
+            _lib.check(L.gf2_lf2_reduce_dev(none._on(stream), P._on(stream), c0, b, cptr, None, None, stream), "gf2_lf2_reduce_dev")
+            cap = int(own_c.read(stream)[0])
+            if cap >= 1 << 31:
+                raise ValueError("lf2_reduce: %d pairs do not fit a matrix; give D or cap" % cap)
+        D = DMat(cap, P.ncols)
+    own_l = _IntScratch(D.nrows) if lo is None and D.nrows > 0 else None
+    own_h = _IntScratch(D.nrows) if hi is None and D.nrows > 0 else None
+    lptr, hptr = own_l.ptr if own_l else (lo or None), own_h.ptr if own_h else (hi or None)
+    _lib.check(L.gf2_lf2_reduce_dev(D._on(stream), P._on(stream), c0, b, cptr, lptr, hptr, stream), "gf2_lf2_reduce_dev")
+    for own in (own_c, own_l, own_h):
+        if own:
+            own.mat._streams.add(stream)
+    return D, own_c, own_l, own_h
 
 
 class CoverCode:
