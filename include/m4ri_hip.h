@@ -191,7 +191,8 @@ mzd_t *mzd_kernel_left_pluq(mzd_t *A, int cutoff);
 /* A dense bit matrix in device memory: row-major 64-bit words, LSB-first, `ld` words between
  * rows (ld even, base 16-byte aligned), excess bits of the last word zero.  Entries that say "accepts 8-byte-aligned rows" also take
  * views with an odd `ld` or a base at an odd word; the elimination-family entries (echelonize, inverse, ple, apply_p, trsm, solve,
- * nullspace) keep the rule in the parentheses.
+ * nullspace) keep the rule in the parentheses.  tests/test_gpu_mul_views.py holds gf2_mul_dev, gf2_mul_nt_dev and gf2_transpose_dev to
+ * it: every route on such views of buffers full of random bits, bit for bit, the words around the views included.
  * Two size limits lie above the shapes callers usually have; both are tested past them, bit for bit (tests/test_gpu_limits.py):
  *  - more than 65 536 x 64 = 4 194 304 rows or columns: gf2_transpose_dev, mzd_transpose, gf2_mul_nt_dev and the products that
  *    transpose B put one workgroup per 64 rows into the y dimension of a launch.  The HIP runtime accepts gridDim.y = 65 538 on this
@@ -260,12 +261,14 @@ int gf2_dmat_fill_random_block(gf2_dmat *M, uint64_t seed, int64_t row0, int64_t
  * bound the automatic choice only.
  * Aliasing: A and B are only read -- A may be B (squaring) and the two may overlap; C is stored tile by tile while other workgroups
  * still read those rows of A and B, so C may share no word with either, with or without `accumulate` (-1, "overlap").  C, A and B may
- * be three disjoint column ranges of one parent.  Accepts 8-byte-aligned rows (an odd `ld` takes the plain path instead of Strassen).
+ * be three disjoint column ranges of one parent.  Accepts 8-byte-aligned rows (tests/test_gpu_mul_views.py): the Strassen passes work
+ * on the caller's buffers only when every `ld` is even and every base 16-byte aligned; a product with an odd `ld` or a base at an odd
+ * word takes the plain path instead, or, from 1024 rows on, may run its levels on zero-padded copies.
  * An empty C returns 0; an inner dimension of 0 clears C (accumulate: leaves it). */
 int gf2_mul_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *B, int accumulate, int algo, int param,
                 void *stream);
 /* C (+)= A * Bt^T (row-parity form, mzd.rs:154-168).  Aliasing as gf2_mul_dev: A may be Bt (the Gram matrix A A^T) or overlap it; C
- * may share no word with A or Bt.  Accepts 8-byte-aligned rows. */
+ * may share no word with A or Bt.  Accepts 8-byte-aligned rows (tests/test_gpu_mul_views.py). */
 int gf2_mul_nt_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *Bt, int accumulate, void *stream);
 /* C = A xor B (mzd.rs:223).  Aliasing: C may be identical to A, to B, or to both (same `data`, `ld` and shape: mzd_add(A, A, B), the
  * reference's +=; every word is read and written by the one thread that owns it), and A may be B (the result is zero).  A C that shares
@@ -275,7 +278,7 @@ int gf2_mul_nt_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *Bt, int accum
 int gf2_add_dev(gf2_dmat *C, gf2_dmat const *A, gf2_dmat const *B, void *stream);
 /* D = S^T (mzd.rs:148).  Aliasing: D may share no word with S (-1, "overlap"): there is no in-place transposition, not for a square
  * matrix either; D and S may be disjoint column ranges of one parent.  Accepts 8-byte-aligned rows (both kernels read and write caller
- * memory one 8-byte word at a time). */
+ * memory one 8-byte word at a time; tests/test_gpu_mul_views.py). */
 int gf2_transpose_dev(gf2_dmat *D, gf2_dmat const *S, void *stream);
 /* equality (mzd.rs:187; *equal = 1/0; different shapes: 0; two empty matrices of one shape: 1 without a launch).  Both matrices are only
  * read, so any aliasing is allowed: A is B gives *equal = 1.  Accepts 8-byte-aligned rows (8-byte reads).  Synchronous. */
