@@ -246,6 +246,18 @@ _LF2_PROTOS = {
 }
 LF2_SYMBOLS = tuple(_LF2_PROTOS)
 
+# ... and include/m4ri_hip_draw.h (tests/test_draw_contract.py)
+DRAW_BERNOULLI, DRAW_INDICES, DRAW_SUBSETS, DRAW_PERMUTATION = 1, 2, 3, 4
+_DRAW_PROTOS = {
+    "gf2_bernoulli_dev": (_I, [DMatP, ctypes.c_uint32, ctypes.c_uint64, _I, ctypes.c_void_p]),
+    "gf2_bernoulli_block_dev": (_I, [DMatP, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _I, _I, ctypes.c_void_p]),
+    "gf2_draw_indices_dev": (_I, [ctypes.c_void_p, ctypes.c_longlong, _I, ctypes.c_uint64, ctypes.c_void_p]),
+    "gf2_draw_subsets_dev": (_I, [ctypes.c_void_p, _I, _I, _I, ctypes.c_uint64, _I, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_draw_permutation_dev": (_I, [ctypes.c_void_p, _I, ctypes.c_uint64, ctypes.c_void_p]),
+    "gf2_draw_plan": (_I, [_I, ctypes.c_longlong, _I, ctypes.c_uint32, ctypes.POINTER(ctypes.c_longlong)]),
+}
+DRAW_SYMBOLS = tuple(_DRAW_PROTOS)
+
 _lib = None
 
 
@@ -258,7 +270,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C m4ri-rust_amd/csrc`). There is no fallback for the HIP multiply path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        tables = (_PROTOS, _GATHER_PROTOS, _WEIGHT_PROTOS, _WHT_PROTOS, _BKW_PROTOS, _COVER_PROTOS, _LF2_PROTOS)
+        tables = (_PROTOS, _GATHER_PROTOS, _WEIGHT_PROTOS, _WHT_PROTOS, _BKW_PROTOS, _COVER_PROTOS, _LF2_PROTOS, _DRAW_PROTOS)
         for name, (res, args) in [item for table in tables for item in table.items()]:
             fn = getattr(handle, name)
             fn.restype = res

@@ -57,6 +57,7 @@ enum Gf2ScratchSlot {
   GF2_SLOT_BKW_BLOCK_COUNTS = 11,      // bkw/bkw_host.cpp: block counts of the compaction of gf2_lf1_reduce_dev
   GF2_SLOT_LF2_SORT = 12,              // lf2/lf2_host.cpp: pair buffers and digit counts of the class sort
   GF2_SLOT_LF2_PAIRS = 13,             // lf2/lf2_host.cpp: sorted order, sorted keys and run sums of gf2_lf2_reduce_dev
+  GF2_SLOT_DRAW_PERM = 14,             // draw/draw_host.cpp: pair buffers and digit counts of the sort of gf2_draw_permutation_dev
 };
 int gf2_stream_scratch(hipStream_t s, size_t bytes, void **out, int slot);  // slot: a Gf2ScratchSlot
 // counts a run of a host routine of the size dispatch (gf2_host_small_calls)

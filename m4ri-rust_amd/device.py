@@ -75,6 +75,10 @@ class DMat:
     def fill_random(self, seed, stream=None):
         _lib.check(_lib.lib().gf2_dmat_fill_random(self._on(stream), seed, stream), "gf2_dmat_fill_random")
 
+    def bernoulli_(self, thr, seed, accumulate=False, stream=None):
+        """In place: every bit (accumulate: ^)= 1 with probability thr / 2^32 (include/m4ri_hip_draw.h) -> self."""
+        return bernoulli(self, thr, seed, accumulate=accumulate, stream=stream)
+
     @staticmethod
     def from_host(bm, stream=None):
         m = DMat(bm.nrows(), bm.ncols())
@@ -661,6 +665,90 @@ def lf2_reduce(P, c0, b, D=None, cap=None, count=None, lo=None, hi=None, stream=
         if own:
             own.mat._streams.add(stream)
     return D, own_c, own_l, own_h
+
+
+def draw_plan(what, count_or_k=0, n=1, thr=0):
+    """How a draw runs (include/m4ri_hip_draw.h, no device needed); what: "bernoulli" -> (Philox calls per output word for thr, threads
+    per workgroup, lanes of one pass of the grid, 0); "indices" (count, n) -> (Philox calls, threads, draws of one pass of the grid,
+    0); "subsets" (k, n) -> (threads, LDS bytes, subsets per workgroup, the rounds of max_rounds=0); "permutation" (n) -> (scratch
+    bytes, sort passes, key bits, 0); None for a bad shape."""
+    code = {"bernoulli": _lib.DRAW_BERNOULLI, "indices": _lib.DRAW_INDICES, "subsets": _lib.DRAW_SUBSETS,
+            "permutation": _lib.DRAW_PERMUTATION}.get(what, what)
+    out = (ctypes.c_longlong * 4)()
+    rc = _lib.lib().gf2_draw_plan(code, count_or_k, n, thr, out)
+    return None if rc < 0 else tuple(int(x) for x in out)
+
+
+def bernoulli(D, thr, seed, accumulate=False, row0=0, col_word0=0, full_ncols=0, stream=None):
+    """Every bit of D (accumulate: ^)= 1 with probability thr / 2^32, by the Philox rule of include/m4ri_hip_draw.h -> D.  With row0,
+    col_word0 (in 64-bit words) and full_ncols, D is that rectangle of the noise of a matrix of full_ncols columns.  Asynchronous on
+    `stream`."""
+    L = _lib.lib()
+    if row0 or col_word0 or full_ncols:
+        rc = L.gf2_bernoulli_block_dev(D._on(stream), thr, seed, row0, col_word0, full_ncols, int(bool(accumulate)), stream)
+        _lib.check(rc, "gf2_bernoulli_block_dev")
+    else:
+        _lib.check(L.gf2_bernoulli_dev(D._on(stream), thr, seed, int(bool(accumulate)), stream), "gf2_bernoulli_dev")
+    return D
+
+
+def _draw_ints(name, call, count, out, stream):
+    """the int output of a draw: `out` is a raw device address (the call only enqueues, None is returned) or None: the wrapper
+    allocates the array and returns it as an object with .ptr and .read(stream)"""
+    own = None
+    if out is None:
+        own = _IntScratch(max(count, 1))   # an address even where nothing is drawn
+        own.count = count
+    _lib.check(call(own.ptr if own else out), name)
+    if own:
+        own.mat._streams.add(stream)
+    return own
+
+
+def draw_indices(count, n, seed, out=None, stream=None):
+    """`count` independent draws from [0, n) (include/m4ri_hip_draw.h); they feed gather_rows as the device array they are.  `out` is
+    a raw device address of count int32 -- the call only enqueues on `stream`, None is returned -- or None: the wrapper allocates the
+    array and returns it as an object with .ptr and .read(stream) (numpy, waits)."""
+    L = _lib.lib()
+    return _draw_ints("gf2_draw_indices_dev", lambda p: L.gf2_draw_indices_dev(p, count, n, seed, stream), count, out, stream)
+
+
+def draw_subsets(batch, k, n, seed, max_rounds=0, out=None, unfinished=None, stream=None):
+    """`batch` ordered k-tuples of distinct values from [0, n), one per guess of a pooled-Gauss round (include/m4ri_hip_draw.h)
+    -> (sub, unfinished).  Each is a raw device address (batch * k int32; one int32) -- None is returned in its place -- or None: the
+    wrapper allocates it and returns an object with .ptr and .read(stream).  unfinished=SKIP (0): not wanted.  A position that has not
+    settled after max_rounds rounds (0: 64) reads -1.  The call only enqueues on `stream`."""
+    L = _lib.lib()
+    own_u = _IntScratch(1) if unfinished is None else None
+    uptr = own_u.ptr if own_u else (unfinished or None)
+    own_s = _draw_ints("gf2_draw_subsets_dev", lambda p: L.gf2_draw_subsets_dev(p, batch, k, n, seed, max_rounds, uptr, stream),
+                       batch * k, out, stream)
+    if own_u:
+        own_u.mat._streams.add(stream)
+    return own_s, own_u
+
+
+def draw_permutation(n, seed, out=None, stream=None):
+    """A permutation of 0 .. n - 1: the stable argsort of 30-bit Philox keys (include/m4ri_hip_draw.h); it feeds gather_cols and
+    gather_rows as the device array it is.  `out` as in draw_indices()."""
+    L = _lib.lib()
+    return _draw_ints("gf2_draw_permutation_dev", lambda p: L.gf2_draw_permutation_dev(p, n, seed, stream), n, out, stream)
+
+
+def lpn_samples(N, k, secret, thr, seed, stream=None):
+    """N samples of an LPN oracle as an N x (k + 1) DMat [A | A s ^ e]: A is the uniform fill of `seed` (gf2_dmat_fill_random), e
+    Bernoulli(thr / 2^32) noise of the same seed.  `secret` is a k x 1 DMat or k bits (uploaded).  A chain of existing entries --
+    fill, mul, bernoulli(accumulate), concat -- that only enqueues on `stream` when the secret is on the device already."""
+    if not isinstance(secret, DMat):
+        bits = np.asarray(secret).reshape(-1)
+        if len(bits) != k:
+            raise ValueError("lpn_samples: the secret holds %d bits, k is %d" % (len(bits), k))
+        secret = DMat.from_words((bits != 0).astype(np.uint64).reshape(k, 1), 1, stream)
+    A = DMat(N, k)
+    A.fill_random(seed, stream)
+    y = mul(A, secret, stream=stream)
+    bernoulli(y, thr, seed, accumulate=True, stream=stream)
+    return concat(A, y, stream=stream)
 
 
 class CoverCode:
