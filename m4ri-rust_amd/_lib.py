@@ -258,6 +258,14 @@ _DRAW_PROTOS = {
 }
 DRAW_SYMBOLS = tuple(_DRAW_PROTOS)
 
+# ... and include/m4ri_hip_join.h (tests/test_join_contract.py)
+_JOIN_PROTOS = {
+    "gf2_join_dev": (_I, [DMatP, DMatP, DMatP, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _I, _I,
+                          ctypes.c_void_p]),
+    "gf2_join_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
+}
+JOIN_SYMBOLS = tuple(_JOIN_PROTOS)
+
 _lib = None
 
 
@@ -270,7 +278,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C m4ri-rust_amd/csrc`). There is no fallback for the HIP multiply path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        tables = (_PROTOS, _GATHER_PROTOS, _WEIGHT_PROTOS, _WHT_PROTOS, _BKW_PROTOS, _COVER_PROTOS, _LF2_PROTOS, _DRAW_PROTOS)
+        tables = (_PROTOS, _GATHER_PROTOS, _WEIGHT_PROTOS, _WHT_PROTOS, _BKW_PROTOS, _COVER_PROTOS, _LF2_PROTOS, _DRAW_PROTOS, _JOIN_PROTOS)
         for name, (res, args) in [item for table in tables for item in table.items()]:
             fn = getattr(handle, name)
             fn.restype = res

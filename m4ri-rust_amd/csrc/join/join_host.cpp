@@ -1,0 +1,125 @@
+// join_host.cpp -- gf2_join_dev and gf2_join_plan (include/m4ri_hip_join.h; kernels: gf2_join.hip).  Every
+// argument is checked before a device is required and before the first HIP call, so a bad call fails the same way with and without a
+// device; the aliasing check comes last.  The entry only enqueues on the caller's stream: no host synchronisation, no hipMalloc (the
+// sort's work space, the sorted orders and keys of A and B and the run sums come from the stream's scratch arena and are written
+// before they are read).
+#include <stdint.h>
+
+#include <string>
+
+#include "../../../include/m4ri_hip_join.h"
+#include "../dev_args.h"
+#include "../lf2/gf2_lf2.h"
+#include "gf2_join.h"
+#include "join_plan.h"
+
+namespace {
+
+struct FlatArray {
+  const char *name;
+  const void *p;
+  long long bytes;
+};
+
+struct NamedMat {
+  const char *name;
+  gf2_dmat const *m;
+};
+
+// every array against the three matrices and against the arrays before it
+int refuse_array_overlaps(const char *fn, const FlatArray *arrays, int n, const NamedMat *mats, int nmats) {
+  for (int i = 0; i < n; ++i) {
+    if (!arrays[i].p) continue;
+    for (int k = 0; k < nmats; ++k)
+      if (gf2_range_meets_mat(arrays[i].p, arrays[i].bytes, mats[k].m))
+        return gf2_bad_arg(fn, std::string(arrays[i].name) + " and " + mats[k].name + " overlap: the address range of " + arrays[i].name +
+                                   " may not meet " + mats[k].name + "'s");
+    for (int j = 0; j < i; ++j)
+      if (arrays[j].p && gf2_ranges_meet(arrays[i].p, arrays[i].bytes, arrays[j].p, arrays[j].bytes))
+        return gf2_bad_arg(fn, std::string(arrays[j].name) + " and " + arrays[i].name + " overlap: their address ranges may not meet");
+  }
+  return 0;
+}
+
+// order and skeys <- the stable sort of M's rows by their key, in the work space `work` (join_plan: sort_bytes).  M->nrows > 0; the
+// caller holds gf2_enqueue_mu.  The sort of lf2/gf2_lf2.hip, the way lf2_host.cpp and draw_host.cpp run it
+int enqueue_sort(const char *fn, gf2_dmat const *M, int c0, int b, char *work, int *order, int *skeys, hipStream_t s) {
+  const Lf2Plan plan = lf2_plan(M->nrows, M->ncols, b);
+  if (plan.passes == 0) return gf2_hip_rc(gf2k_lf2_iota(M->nrows, order, skeys, s), fn);
+  void *pairs[2] = {work, work + plan.pair_bytes};
+  int *counts = reinterpret_cast<int *>(work + 2 * plan.pair_bytes);
+  int *parts = reinterpret_cast<int *>(work + 2 * plan.pair_bytes + plan.count_bytes);
+  for (int pass = 0; pass < plan.passes; ++pass) {
+    const bool first = pass == 0, last = pass == plan.passes - 1;
+    const hipError_t e = gf2k_lf2_sort_pass(first ? M->data : nullptr, M->ld, c0, b, first ? nullptr : pairs[(pass - 1) & 1], M->nrows, pass,
+                                            counts, parts, last ? nullptr : pairs[pass & 1], last ? order : nullptr, last ? skeys : nullptr, s);
+    GF2_RC(gf2_hip_rc(e, fn));
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int gf2_join_dev(gf2_dmat *D, gf2_dmat const *A, gf2_dmat const *B, int c0, int b, long long *count, int *ia, int *ib, int *wt,
+                            int wc0, int wc1, void *stream) {
+  static const char fn[] = "gf2_join_dev";
+  if (gf2_check_mat(fn, "A", A)) return -1;
+  if (gf2_check_mat(fn, "B", B)) return -1;
+  if (gf2_check_mat(fn, "D", D)) return -1;
+  if (D->nrows > 0) GF2_RC(gf2_refuse_null(fn, "D.data", D->data));  // also where a row has no word
+  if (b < 0 || b > kJoinMaxB) return gf2_bad_arg(fn, "b = " + std::to_string(b) + " is outside 0 <= b <= " + std::to_string(kJoinMaxB));
+  if (B->ncols != A->ncols || D->ncols != A->ncols)
+    return gf2_bad_arg(fn, "A has " + std::to_string(A->ncols) + " columns, B " + std::to_string(B->ncols) + ", D " + std::to_string(D->ncols) +
+                               ": A->ncols, B->ncols and D->ncols must be equal");
+  if (c0 < 0 || (long long)c0 + b > A->ncols)
+    return gf2_bad_arg(fn, "the columns [c0, c0 + b) = [" + std::to_string(c0) + ", " + std::to_string((long long)c0 + b) +
+                               ") are outside A and B (" + std::to_string(A->ncols) + " columns)");
+  GF2_RC(gf2_check_ptr(fn, "count", count, 8));
+  GF2_RC(gf2_refuse_misaligned(fn, "ia", ia, 4));
+  GF2_RC(gf2_refuse_misaligned(fn, "ib", ib, 4));
+  GF2_RC(gf2_refuse_misaligned(fn, "wt", wt, 4));
+  if (wc0 < 0 || wc0 > wc1 || wc1 > A->ncols)
+    return gf2_bad_arg(fn, "the weight range [wc0, wc1) = [" + std::to_string(wc0) + ", " + std::to_string(wc1) + ") is outside 0 <= wc0 <= wc1 <= " +
+                               std::to_string(A->ncols) + " columns");
+  // aliasing, last.  A and B are only read: they may overlap or be one view
+  GF2_RC(gf2_refuse_overlap(fn, "D", D, "A", A));
+  GF2_RC(gf2_refuse_overlap(fn, "D", D, "B", B));
+  const FlatArray arrays[4] = {{"count", count, 8}, {"ia", ia, 4ll * D->nrows}, {"ib", ib, 4ll * D->nrows}, {"wt", wt, 4ll * D->nrows}};
+  const NamedMat mats[3] = {{"A", A}, {"B", B}, {"D", D}};
+  GF2_RC(refuse_array_overlaps(fn, arrays, 4, mats, 3));
+  GF2_RC(gf2_require_device_for(fn));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (A->nrows == 0 || B->nrows == 0) return gf2_hip_rc(hipMemsetAsync(count, 0, 8, s), fn);
+  const JoinPlan plan = join_plan(A->nrows, B->nrows, A->ncols, b);
+  std::lock_guard<std::mutex> lk(gf2_enqueue_mu);  // another thread on the same stream would be handed the same scratch
+  void *scratch = nullptr;
+  GF2_RC(gf2_stream_scratch(s, (size_t)plan.scratch, &scratch, GF2_SLOT_JOIN));
+  char *base = static_cast<char *>(scratch), *at = base + plan.sort_bytes;
+  int *order_a = reinterpret_cast<int *>(at), *skeys_a = reinterpret_cast<int *>(at + plan.order_a);
+  at += 2 * plan.order_a;
+  int *order_b = reinterpret_cast<int *>(at), *skeys_b = reinterpret_cast<int *>(at + plan.order_b);
+  long long *sums = reinterpret_cast<long long *>(at + 2 * plan.order_b);
+  GF2_RC(enqueue_sort(fn, A, c0, b, base, order_a, skeys_a, s));
+  GF2_RC(enqueue_sort(fn, B, c0, b, base, order_b, skeys_b, s));  // behind A's sort on the stream: the work space is free again
+  GF2_RC(gf2_hip_rc(gf2k_join_count(skeys_a, A->nrows, skeys_b, B->nrows, sums, count, s), fn));
+  if (D->nrows == 0) return 0;  // a count-only call
+  const hipError_t e = gf2k_join_scatter(A->data, A->ld, A->nrows, B->data, B->ld, B->nrows, A->ncols, order_a, skeys_a, order_b, skeys_b, sums,
+                                         D->data, D->ld, D->nrows, ia, ib, wt, wc0, wc1, -1, s);
+  return gf2_hip_rc(e, fn);
+}
+
+extern "C" int gf2_join_plan(int nrows_a, int nrows_b, int ncols, int b, long long out[8]) {
+  const JoinPlan p = join_plan(nrows_a, nrows_b, ncols, b);
+  if (p.passes < 0) return -1;
+  if (out) {
+    out[0] = kJoinThreads;
+    out[1] = kJoinRunRows;
+    out[2] = p.lanes;
+    out[3] = kJoinSpanKeys;
+    out[4] = kJoinLds;
+    out[5] = p.scratch;
+    out[6] = p.runs;
+    out[7] = p.sort_bytes;
+  }
+  return p.passes;
+}

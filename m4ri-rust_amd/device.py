@@ -182,6 +182,14 @@ class DMat:
         (include/m4ri_hip_lf2.h)."""
         return lf2_reduce(self, c0, b, lo=SKIP, hi=SKIP)[0]
 
+    def join(self, other, c0, b, wcols=None):
+        """The join with another pool as a new DMat of exactly `count` rows: the XOR of every pair of a row of self and a row of
+        `other` whose bits [c0, c0 + b) are equal, classes by ascending key, the pairs of a class by (row of self, row of other)
+        (include/m4ri_hip_join.h).  With wcols = (wc0, wc1) -> (D, wt): wt the ones of every row of D in those columns, on the
+        device (.ptr feeds select_weights, .read(stream) gives numpy)."""
+        out = join(self, other, c0, b, ia=SKIP, ib=SKIP, wt=SKIP if wcols is None else None, wcols=wcols)
+        return out[0] if wcols is None else (out[0], out[4])
+
     def cover_reduce(self, c0, segments):
         """The covering-code reduction as a new DMat: the columns from c0 on are cut into blocks as long as the codes of `segments` (a
         list of CoverCode), every block is decoded to its nearest codeword and replaced by the message (include/m4ri_hip_cover.h)."""
@@ -665,6 +673,50 @@ def lf2_reduce(P, c0, b, D=None, cap=None, count=None, lo=None, hi=None, stream=
         if own:
             own.mat._streams.add(stream)
     return D, own_c, own_l, own_h
+
+
+def join_plan(nrows_a, nrows_b, ncols, b):
+    """How the join of nrows_a x ncols with nrows_b x ncols on a window of b bits runs (no device needed) -> (passes of either sort,
+    threads per workgroup, sorted positions of A per run R, lanes per row of the scatter, keys of B a workgroup stages in LDS at the
+    most S, LDS bytes, scratch bytes, runs of A, the sorts' share of the scratch bytes); None for a bad shape."""
+    out = (ctypes.c_longlong * 8)()
+    v = _lib.lib().gf2_join_plan(nrows_a, nrows_b, ncols, b, out)
+    return None if v < 0 else (v,) + tuple(int(x) for x in out)
+
+
+def join(A, B, c0, b, D=None, cap=None, count=None, ia=None, ib=None, wt=None, wcols=None, stream=None):
+    """The join of two pools on a window (include/m4ri_hip_join.h): every pair of a row of A and a row of B whose bits [c0, c0 + b)
+    are equal is XORed.  -> (D, count, ia, ib, wt), all on the device: D holds the pairs, classes by ascending key and the pairs of a
+    class by (row of A, row of B) (D.nrows is the capacity; `count`, an int64, says how many there are in all), ia[t] and ib[t] the
+    rows of A and B that D[t] came from, wt[t] the ones of D[t] in the columns wcols = (wc0, wc1) (None: all columns).  Each of
+    `count`, `ia`, `ib` and `wt` is a raw device address -- the kernels write there, None is returned in its place -- or None: the
+    wrapper allocates the array and returns it as an object with .ptr (which feeds gather_rows / select_weights as it is) and
+    .read(stream) (numpy, waits).  ia / ib / wt = SKIP (0): not wanted.  The capacity is D.nrows, else `cap`; the call then only
+    enqueues on `stream`.  With neither (cap=None), a count-only call comes first, the wrapper WAITS for it and sizes D to exactly
+    count rows.  A may be B: all ordered pairs of a class, (i, i) included."""
+    L = _lib.lib()
+    wc0, wc1 = (0, A.ncols) if wcols is None else wcols
+    own_c = _Int64Scratch() if count is None else None
+    cptr = own_c.ptr if own_c else count
+    if D is None:
+        if cap is None:
+            if own_c is None:
+                raise ValueError("join: a raw count address needs D or cap (the wrapper cannot read the count to size D)")
+            none = DMat.wrap(None, 0, A.ncols, A.ld)
+            rc = L.gf2_join_dev(none._on(stream), A._on(stream), B._on(stream), c0, b, cptr, None, None, None, wc0, wc1, stream)
+            _lib.check(rc, "gf2_join_dev")
+            cap = int(own_c.read(stream)[0])
+            if cap >= 1 << 31:
+                raise ValueError("join: %d pairs do not fit a matrix; give D or cap" % cap)
+        D = DMat(cap, A.ncols)
+    owned = [_IntScratch(D.nrows) if given is None and D.nrows > 0 else None for given in (ia, ib, wt)]
+    ptrs = [own.ptr if own else (given or None) for own, given in zip(owned, (ia, ib, wt))]
+    rc = L.gf2_join_dev(D._on(stream), A._on(stream), B._on(stream), c0, b, cptr, ptrs[0], ptrs[1], ptrs[2], wc0, wc1, stream)
+    _lib.check(rc, "gf2_join_dev")
+    for own in [own_c] + owned:
+        if own:
+            own.mat._streams.add(stream)
+    return (D, own_c) + tuple(owned)
 
 
 def draw_plan(what, count_or_k=0, n=1, thr=0):
