@@ -266,6 +266,17 @@ _JOIN_PROTOS = {
 }
 JOIN_SYMBOLS = tuple(_JOIN_PROTOS)
 
+# ... and include/m4ri_hip_sums.h (tests/test_sums_contract.py)
+_SUMS_PROTOS = {
+    "gf2_subset_sums_dev": (_I, [DMatP, DMatP, DMatP, _I, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, _I, _I, ctypes.c_void_p]),
+    "gf2_unrank_subsets_dev": (_I, [ctypes.c_void_p, _I, ctypes.c_longlong, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_subset_count": (ctypes.c_longlong, [_I, _I]),
+    "gf2_subset_rank": (ctypes.c_longlong, [ctypes.POINTER(_I), _I]),
+    "gf2_subset_unrank": (_I, [ctypes.c_longlong, _I, ctypes.POINTER(_I)]),
+    "gf2_subset_sums_plan": (_I, [_I, _I, _I, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]),
+}
+SUMS_SYMBOLS = tuple(_SUMS_PROTOS)
+
 _lib = None
 
 
@@ -278,7 +289,8 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C m4ri-rust_amd/csrc`). There is no fallback for the HIP multiply path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        tables = (_PROTOS, _GATHER_PROTOS, _WEIGHT_PROTOS, _WHT_PROTOS, _BKW_PROTOS, _COVER_PROTOS, _LF2_PROTOS, _DRAW_PROTOS, _JOIN_PROTOS)
+        tables = (_PROTOS, _GATHER_PROTOS, _WEIGHT_PROTOS, _WHT_PROTOS, _BKW_PROTOS, _COVER_PROTOS, _LF2_PROTOS, _DRAW_PROTOS, _JOIN_PROTOS,
+                  _SUMS_PROTOS)
         for name, (res, args) in [item for table in tables for item in table.items()]:
             fn = getattr(handle, name)
             fn.restype = res

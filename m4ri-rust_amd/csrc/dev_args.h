@@ -24,12 +24,14 @@ static inline int gf2_check_ptr(const char *fn, const std::string &name, const v
   if (int rc = gf2_refuse_null(fn, name, p)) return rc;
   return gf2_refuse_misaligned(fn, name, p, align);
 }
-// a matrix argument that can be addressed: `name` goes into the message
-inline int gf2_check_mat(const char *fn, const char *name, gf2_dmat const *M) {
+// a matrix argument that can be addressed: `name` goes into the message.  unstored_ok: a null `data` on a non-empty matrix is accepted
+// (gf2_subset_sums_dev: the rows are not stored, only the arrays that go with them are written); such a matrix shares no word with
+// anything and meets no address range
+inline int gf2_check_mat(const char *fn, const char *name, gf2_dmat const *M, bool unstored_ok = false) {
   const std::string n(name);
   GF2_RC(gf2_refuse_null(fn, n, M));
   if (M->nrows < 0 || M->ncols < 0) return gf2_bad_arg(fn, n + " has a negative dimension");
-  if (M->nrows > 0 && M->ncols > 0) {
+  if (M->nrows > 0 && M->ncols > 0 && !(unstored_ok && !M->data)) {
     GF2_RC(gf2_check_ptr(fn, n + ".data", M->data, 8));
     if (M->ld < (((long long)M->ncols + 63) >> 6))
       return gf2_bad_arg(fn, n + ".ld is smaller than the row width (the row stride cannot hold a row)");
@@ -65,7 +67,7 @@ inline bool gf2_bit_rects_share(__int128 x0, long long ldx, long long xrows, lon
 }
 // "Do these two views share a word?": the rule above on the whole words of two matrices (an empty matrix shares nothing)
 inline bool gf2_views_share_word(gf2_dmat const *X, gf2_dmat const *Y) {
-  if (X->nrows <= 0 || X->ncols <= 0 || Y->nrows <= 0 || Y->ncols <= 0) return false;
+  if (X->nrows <= 0 || X->ncols <= 0 || Y->nrows <= 0 || Y->ncols <= 0 || !X->data || !Y->data) return false;
   return gf2_bit_rects_share((__int128)reinterpret_cast<uintptr_t>(X->data) * 8, X->ld, X->nrows, (((long long)X->ncols + 63) >> 6) * 64,
                              (__int128)reinterpret_cast<uintptr_t>(Y->data) * 8, Y->ld, Y->nrows, (((long long)Y->ncols + 63) >> 6) * 64);
 }
@@ -92,9 +94,33 @@ static inline __int128 gf2_mat_end(gf2_dmat const *M) {
   return (__int128)reinterpret_cast<uintptr_t>(M->data) + 8 * ((__int128)(M->nrows - 1) * M->ld + (((long long)M->ncols + 63) >> 6));
 }
 static inline bool gf2_range_meets_mat(const void *p, long long bytes, gf2_dmat const *M) {
-  if (M->nrows <= 0 || M->ncols <= 0 || bytes <= 0) return false;
+  if (M->nrows <= 0 || M->ncols <= 0 || bytes <= 0 || !M->data) return false;
   const __int128 a0 = reinterpret_cast<uintptr_t>(p), a1 = a0 + bytes;
   return a0 < gf2_mat_end(M) && (__int128)reinterpret_cast<uintptr_t>(M->data) < a1;
+}
+// the int and count arrays of a call against its matrices and against each other: every array that is given (p != null) against
+// every matrix, then against the arrays before it; "overlap" in the message
+struct Gf2FlatArray {
+  const char *name;
+  const void *p;
+  long long bytes;
+};
+struct Gf2NamedMat {
+  const char *name;
+  gf2_dmat const *m;
+};
+static inline int gf2_refuse_array_overlaps(const char *fn, const Gf2FlatArray *arrays, int n, const Gf2NamedMat *mats, int nmats) {
+  for (int i = 0; i < n; ++i) {
+    if (!arrays[i].p) continue;
+    for (int k = 0; k < nmats; ++k)
+      if (mats[k].m && gf2_range_meets_mat(arrays[i].p, arrays[i].bytes, mats[k].m))
+        return gf2_bad_arg(fn, std::string(arrays[i].name) + " and " + mats[k].name + " overlap: the address range of " + arrays[i].name +
+                                   " may not meet " + mats[k].name + "'s");
+    for (int j = 0; j < i; ++j)
+      if (arrays[j].p && gf2_ranges_meet(arrays[i].p, arrays[i].bytes, arrays[j].p, arrays[j].bytes))
+        return gf2_bad_arg(fn, std::string(arrays[j].name) + " and " + arrays[i].name + " overlap: their address ranges may not meet");
+  }
+  return 0;
 }
 // two matrices by address range, whatever their strides (gf2_inverse_batch_dev: its kernel owns whole stacks)
 static inline bool gf2_mat_ranges_meet(gf2_dmat const *X, gf2_dmat const *Y) {

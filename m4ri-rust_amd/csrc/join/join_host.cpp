@@ -15,32 +15,6 @@
 
 namespace {
 
-struct FlatArray {
-  const char *name;
-  const void *p;
-  long long bytes;
-};
-
-struct NamedMat {
-  const char *name;
-  gf2_dmat const *m;
-};
-
-// every array against the three matrices and against the arrays before it
-int refuse_array_overlaps(const char *fn, const FlatArray *arrays, int n, const NamedMat *mats, int nmats) {
-  for (int i = 0; i < n; ++i) {
-    if (!arrays[i].p) continue;
-    for (int k = 0; k < nmats; ++k)
-      if (gf2_range_meets_mat(arrays[i].p, arrays[i].bytes, mats[k].m))
-        return gf2_bad_arg(fn, std::string(arrays[i].name) + " and " + mats[k].name + " overlap: the address range of " + arrays[i].name +
-                                   " may not meet " + mats[k].name + "'s");
-    for (int j = 0; j < i; ++j)
-      if (arrays[j].p && gf2_ranges_meet(arrays[i].p, arrays[i].bytes, arrays[j].p, arrays[j].bytes))
-        return gf2_bad_arg(fn, std::string(arrays[j].name) + " and " + arrays[i].name + " overlap: their address ranges may not meet");
-  }
-  return 0;
-}
-
 // order and skeys <- the stable sort of M's rows by their key, in the work space `work` (join_plan: sort_bytes).  M->nrows > 0; the
 // caller holds gf2_enqueue_mu.  The sort of lf2/gf2_lf2.hip, the way lf2_host.cpp and draw_host.cpp run it
 int enqueue_sort(const char *fn, gf2_dmat const *M, int c0, int b, char *work, int *order, int *skeys, hipStream_t s) {
@@ -84,9 +58,9 @@ extern "C" int gf2_join_dev(gf2_dmat *D, gf2_dmat const *A, gf2_dmat const *B, i
   // aliasing, last.  A and B are only read: they may overlap or be one view
   GF2_RC(gf2_refuse_overlap(fn, "D", D, "A", A));
   GF2_RC(gf2_refuse_overlap(fn, "D", D, "B", B));
-  const FlatArray arrays[4] = {{"count", count, 8}, {"ia", ia, 4ll * D->nrows}, {"ib", ib, 4ll * D->nrows}, {"wt", wt, 4ll * D->nrows}};
-  const NamedMat mats[3] = {{"A", A}, {"B", B}, {"D", D}};
-  GF2_RC(refuse_array_overlaps(fn, arrays, 4, mats, 3));
+  const Gf2FlatArray arrays[4] = {{"count", count, 8}, {"ia", ia, 4ll * D->nrows}, {"ib", ib, 4ll * D->nrows}, {"wt", wt, 4ll * D->nrows}};
+  const Gf2NamedMat mats[3] = {{"A", A}, {"B", B}, {"D", D}};
+  GF2_RC(gf2_refuse_array_overlaps(fn, arrays, 4, mats, 3));
   GF2_RC(gf2_require_device_for(fn));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (A->nrows == 0 || B->nrows == 0) return gf2_hip_rc(hipMemsetAsync(count, 0, 8, s), fn);

@@ -190,6 +190,11 @@ class DMat:
         out = join(self, other, c0, b, ia=SKIP, ib=SKIP, wt=SKIP if wcols is None else None, wcols=wcols)
         return out[0] if wcols is None else (out[0], out[4])
 
+    def subset_sums(self, p, base=None):
+        """All C(nrows, p) XORs of p rows of self (each ^ base, a 1-row DMat, if given) as a new DMat, in the colexicographic order of
+        the subsets: row C(c_1, 1) + ... + C(c_p, p) is the sum of the rows c_1 < ... < c_p (include/m4ri_hip_sums.h)."""
+        return subset_sums(self, p, base=base, idx=SKIP, wt=SKIP)[0]
+
     def cover_reduce(self, c0, segments):
         """The covering-code reduction as a new DMat: the columns from c0 on are cut into blocks as long as the codes of `segments` (a
         list of CoverCode), every block is decoded to its nearest codeword and replaced by the message (include/m4ri_hip_cover.h)."""
@@ -717,6 +722,93 @@ def join(A, B, c0, b, D=None, cap=None, count=None, ia=None, ib=None, wt=None, w
         if own:
             own.mat._streams.add(stream)
     return (D, own_c) + tuple(owned)
+
+
+def subset_count(n, p):
+    """C(n, p), the number of subsets that subset_sums(S, p) of n rows enumerates (no device needed); 0 for n < p; None for a p outside
+    1 .. 4 or a value past 2^62."""
+    v = _lib.lib().gf2_subset_count(n, p)
+    return None if v < 0 else int(v)
+
+
+def subset_sums_plan(n, ncols, p, count):
+    """How `count` sums of p of n rows of ncols columns run (include/m4ri_hip_sums.h, no device needed) -> (kernel id: 0 .. 3 S in LDS
+    with 1, 2, 8, 64 lanes per row, 4 .. 7 S from global memory likewise; threads per workgroup; ranks per workgroup R; lanes per row;
+    LDS bytes; workgroups; scratch bytes); None for a bad shape."""
+    out = (ctypes.c_longlong * 6)()
+    v = _lib.lib().gf2_subset_sums_plan(n, ncols, p, count, out)
+    return None if v < 0 else (v,) + tuple(int(x) for x in out)
+
+
+class _TupleScratch(_IntScratch):
+    """count tuples of p device ints (the idx of subset_sums / unrank_subsets); read() gives shape (count, p)"""
+
+    def __init__(self, count, p):
+        _IntScratch.__init__(self, count * p)
+        self.p = p
+
+    def read(self, stream):
+        return _IntScratch.read(self, stream).reshape(-1, self.p)
+
+
+def subset_sums(S, p, base=None, rank0=0, count=None, D=None, idx=None, wt=None, wcols=None, store=True, stream=None):
+    """All XORs of p rows of S in rank order (include/m4ri_hip_sums.h): D[t] = base ^ S[c_1] ^ ... ^ S[c_p] for the subset c_1 < ... <
+    c_p of rank rank0 + t in the colexicographic order, rank = C(c_1, 1) + ... + C(c_p, p).  -> (D, idx, wt), all on the device:
+    idx[t] = (c_1 .. c_p), wt[t] the ones of D[t] in the columns wcols = (wc0, wc1) (None: all columns).  base: None or a 1-row DMat
+    (the syndrome).  The window is D.nrows rows, else `count`, else (count=None) everything from rank0 up to C(n, p); ValueError when
+    that does not fit a matrix (2^31 - 1 rows).  store=False: the rows are not stored -- no D is allocated, None is returned in its
+    place and only idx and wt are written (the weights of all candidates of Lee-Brickell).  Each of `idx` and `wt` is a raw device
+    address -- the kernel writes there, None is returned in its place -- or None: the wrapper allocates the array and returns it as
+    an object with .ptr (wt feeds select_weights, idx gather_rows as they are) and .read(stream) (numpy, waits; idx: shape
+    (count, p)); SKIP (0): not wanted.  The call only enqueues on `stream`."""
+    total = subset_count(S.nrows, p)
+    if total is None:
+        raise ValueError("subset_sums: p = %d is outside 1 .. 4, or C(%d, %d) passes 2^62" % (p, S.nrows, p))
+    if D is not None:
+        if not store:
+            raise ValueError("subset_sums: store=False takes no D")
+        if count is not None and count != D.nrows:
+            raise ValueError("subset_sums: count = %d, but D has %d rows" % (count, D.nrows))
+        count = D.nrows
+    if count is None:
+        count = max(total - rank0, 0)
+    if count >= 1 << 31:
+        raise ValueError("subset_sums: %d sums do not fit a matrix; give count, D or rank0" % count)
+    if D is None:
+        D = DMat(count, S.ncols) if store else DMat.wrap(None, count, S.ncols, max((S.ncols + 63) // 64, 1))
+    wc0, wc1 = (0, S.ncols) if wcols is None else wcols
+    own_i = _TupleScratch(count, p) if idx is None and count > 0 else None
+    own_w = _IntScratch(count) if wt is None and count > 0 else None
+    iptr, wptr = own_i.ptr if own_i else (idx or None), own_w.ptr if own_w else (wt or None)
+    rc = _lib.lib().gf2_subset_sums_dev(D._on(stream), S._on(stream), base._on(stream) if base is not None else None, p, rank0, iptr, wptr,
+                                        wc0, wc1, stream)
+    _lib.check(rc, "gf2_subset_sums_dev")
+    for own in (own_i, own_w):
+        if own:
+            own.mat._streams.add(stream)
+    return (D if store else None), own_i, own_w
+
+
+def unrank_subsets(ranks, count, p, n, rank0=0, idx=None, bad=None, stream=None):
+    """The subsets of the ranks rank0 + ranks[t], t < count, of the order of subset_sums over n rows -> (idx, bad): idx[t] = (c_1 ..
+    c_p); a rank of -1 (what select_weights leaves behind its count) gives p times -1, any other rank outside [0, C(n, p)) as well
+    and is reported in `bad`.  `ranks` is a raw device address of count int32 (what select_weights wrote, or the ia / ib of a join
+    gathered at the hits) or a list / numpy int array that the wrapper uploads.  `idx` is a raw device address of count * p int32 --
+    None is returned in its place -- or None: the wrapper allocates the array and returns it as an object with .ptr and
+    .read(stream) (numpy of shape (count, p), waits).  `bad` follows gather_rows(): a raw device address of an int the caller has
+    zeroed, or SKIP (0) -- the call then only enqueues on `stream` and None is returned in its place -- or None: the wrapper
+    allocates a zeroed int, WAITS for `stream` and returns a bool."""
+    rptr, keep = _device_ints(ranks, count, "unrank_subsets", stream)
+    own_i = _TupleScratch(count, p) if idx is None and count > 0 else None
+    own_b = None
+    if bad is None:
+        own_b = _IntUpload([0], stream)
+        bad = own_b.ptr
+    rc = _lib.lib().gf2_unrank_subsets_dev(rptr, count, rank0, p, n, own_i.ptr if own_i else (idx or None), bad or None, stream)
+    _lib.check(rc, "gf2_unrank_subsets_dev")
+    if own_i:
+        own_i.mat._streams.add(stream)
+    return own_i, (bool(own_b.read(stream)[0]) if own_b else None)
 
 
 def draw_plan(what, count_or_k=0, n=1, thr=0):
