@@ -289,6 +289,8 @@ int join_rows_aligned16(const u64 *M, long long ld, long long nrows, long long n
   return nw > 1 && !(reinterpret_cast<uintptr_t>(M) & 15) && (!(ld & 1) || nrows == 1);
 }
 
+#include "gf2_join_select.inc"  // gf2_join_weigh_kernel / gf2_join_select_scatter_kernel and their launchers: the weight-filtered join
+
 }  // namespace
 
 extern "C" hipError_t gf2k_join_count(const int *skeys_a, int nrows_a, const int *skeys_b, int nrows_b, long long *sums, long long *count,

@@ -39,3 +39,30 @@ inline JoinPlan join_plan(long long nrows_a, long long nrows_b, long long ncols,
   p.scratch = p.sort_bytes + 2 * p.order_a + 2 * p.order_b + lf2_align16(8 * p.runs);
   return p;
 }
+
+// ---- the weight-filtered join (gf2_join_select_dev; kernels: gf2_join_select.inc)
+// LDS of its scatter kernel: the join's, and two rows of the waves' hits of a round
+constexpr int kJoinSelectLds = kJoinLds + 2 * 4 * kJoinWaves;
+
+struct JoinSelectPlan {
+  JoinPlan join;        // sorts, runs, lanes per row of the row store and the join's scratch, as they are
+  int weigh_lanes;      // lanes per pair of the weigh pass: by the words of a row that hold a column of the weight range
+  int round_outputs;    // outputs per round of the scatter: one per group of join.lanes lanes
+  long long hit_bytes;  // the hit sums: one array of a long long per run, twice (the scan turns one into offsets, the other stays)
+  long long scratch;    // all of it: the join's scratch, then the hit sums
+};
+
+// wc0 <= wc1: the weight range, checked by the caller (an empty one holds no word)
+inline JoinSelectPlan join_select_plan(long long nrows_a, long long nrows_b, long long ncols, int b, long long wc0, long long wc1) {
+  JoinSelectPlan p;
+  p.join = join_plan(nrows_a, nrows_b, ncols, b);
+  p.weigh_lanes = p.round_outputs = 0;
+  p.hit_bytes = p.scratch = 0;
+  if (p.join.passes < 0) return p;
+  const long long words = wc0 < wc1 ? ((wc1 - 1) >> 6) - (wc0 >> 6) + 1 : 0;
+  p.weigh_lanes = words <= kLf2PieceWords ? 1 : words <= kLf2NarrowWords ? 2 : words <= kLf2MidWords ? 8 : 64;
+  p.round_outputs = kJoinThreads / p.join.lanes;
+  p.hit_bytes = 2 * lf2_align16(8 * p.join.runs);
+  p.scratch = p.join.scratch + p.hit_bytes;
+  return p;
+}

@@ -190,6 +190,13 @@ class DMat:
         out = join(self, other, c0, b, ia=SKIP, ib=SKIP, wt=SKIP if wcols is None else None, wcols=wcols)
         return out[0] if wcols is None else (out[0], out[4])
 
+    def join_select(self, other, c0, b, wcols, wlo, whi):
+        """The hits of the join with another pool as a new DMat of exactly `hits` rows: of the pairs of join(), in its order, those
+        whose XOR has between wlo and whi ones in the columns wcols = (wc0, wc1) (include/m4ri_hip_join_select.h) -> (D, ia, ib, wt):
+        the rows of self and of `other` and the weight of every hit, on the device (.ptr, .read(stream))."""
+        out = join_select(self, other, c0, b, wcols, wlo, whi)
+        return (out[0],) + out[3:]
+
     def subset_sums(self, p, base=None):
         """All C(nrows, p) XORs of p rows of self (each ^ base, a 1-row DMat, if given) as a new DMat, in the colexicographic order of
         the subsets: row C(c_1, 1) + ... + C(c_p, p) is the sum of the rows c_1 < ... < c_p (include/m4ri_hip_sums.h)."""
@@ -722,6 +729,56 @@ def join(A, B, c0, b, D=None, cap=None, count=None, ia=None, ib=None, wt=None, w
         if own:
             own.mat._streams.add(stream)
     return (D, own_c) + tuple(owned)
+
+
+def join_select_plan(nrows_a, nrows_b, ncols, b, wcols=None):
+    """How the weight-filtered join runs (include/m4ri_hip_join_select.h, no device needed) -> (passes of either sort, threads per
+    workgroup, sorted positions of A per run R, lanes per pair of the weigh pass (by the words of the weight range wcols), lanes per
+    row of the row store (by the row width), LDS bytes, scratch bytes, runs of A, outputs per round of the scatter G); None for a bad
+    shape or range."""
+    wc0, wc1 = (0, ncols) if wcols is None else wcols
+    out = (ctypes.c_longlong * 8)()
+    v = _lib.lib().gf2_join_select_plan(nrows_a, nrows_b, ncols, b, wc0, wc1, out)
+    return None if v < 0 else (v,) + tuple(int(x) for x in out)
+
+
+def join_select(A, B, c0, b, wcols, wlo, whi, D=None, cap=None, store=True, count=None, hits=None, ia=None, ib=None, wt=None, stream=None):
+    """The weight-filtered join (include/m4ri_hip_join_select.h): of the pairs of join(A, B, c0, b), in its order, only the HITS -- those
+    whose XOR has between wlo and whi ones in the columns wcols = (wc0, wc1) (None: all columns) -- are written.  -> (D, count, hits,
+    ia, ib, wt), all on the device: D[h], ia[h], ib[h], wt[h] for the h-th hit; `count`, an int64, the number of all pairs and `hits`,
+    an int64, the number of all hits, which may exceed the capacity.  The arrays follow join(): a raw device address (None is
+    returned in its place), None (the wrapper allocates the array and returns an object with .ptr and .read(stream)), and for ia / ib
+    / wt SKIP (0): not wanted.  The capacity is D.nrows, else `cap`; the call then only enqueues on `stream`.  With neither, a
+    counts-only call comes first, the wrapper WAITS for it and sizes D to exactly `hits` rows.  store=False: the rows are not stored
+    -- D is passed without data, None is returned in its place and only ia, ib and wt are written (the index-only mode)."""
+    L = _lib.lib()
+    wc0, wc1 = (0, A.ncols) if wcols is None else wcols
+    own_c = _Int64Scratch() if count is None else None
+    own_h = _Int64Scratch() if hits is None else None
+    cptr, hptr = own_c.ptr if own_c else count, own_h.ptr if own_h else hits
+
+    def call(Dm, pa, pb, pw):
+        rc = L.gf2_join_select_dev(Dm._on(stream), A._on(stream), B._on(stream), c0, b, wc0, wc1, wlo, whi, cptr, hptr, pa, pb, pw, stream)
+        _lib.check(rc, "gf2_join_select_dev")
+
+    if D is not None and not store:
+        raise ValueError("join_select: store=False takes no D")
+    if D is None:
+        if cap is None:
+            if own_h is None:
+                raise ValueError("join_select: a raw hits address needs D or cap (the wrapper cannot read the hits to size D)")
+            call(DMat.wrap(None, 0, A.ncols, A.ld), None, None, None)
+            cap = int(own_h.read(stream)[0])
+            if cap >= 1 << 31:
+                raise ValueError("join_select: %d hits do not fit a matrix; give D or cap" % cap)
+        D = DMat(cap, A.ncols) if store else DMat.wrap(None, cap, A.ncols, max((A.ncols + 63) // 64, 1))
+    owned = [_IntScratch(D.nrows) if given is None and D.nrows > 0 else None for given in (ia, ib, wt)]
+    ptrs = [own.ptr if own else (given or None) for own, given in zip(owned, (ia, ib, wt))]
+    call(D, *ptrs)
+    for own in [own_c, own_h] + owned:
+        if own:
+            own.mat._streams.add(stream)
+    return (D if store else None, own_c, own_h) + tuple(owned)
 
 
 def subset_count(n, p):
