@@ -285,6 +285,15 @@ _JOIN_SELECT_PROTOS = {
 }
 JOIN_SELECT_SYMBOLS = tuple(_JOIN_SELECT_PROTOS)
 
+# ... and include/m4ri_hip_near.h (tests/test_near_contract.py)
+_NEAR_PROTOS = {
+    "gf2_near_pairs_dev": (_I, [DMatP, DMatP, DMatP, _I, _I, _I, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.c_void_p]),
+    "gf2_nearest_dev": (_I, [DMatP, DMatP, _I, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_near_plan": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
+}
+NEAR_SYMBOLS = tuple(_NEAR_PROTOS)
+
 _lib = None
 
 
@@ -298,7 +307,7 @@ def lib():
                 "(or `make -C m4ri-rust_amd/csrc`). There is no fallback for the HIP multiply path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         tables = (_PROTOS, _GATHER_PROTOS, _WEIGHT_PROTOS, _WHT_PROTOS, _BKW_PROTOS, _COVER_PROTOS, _LF2_PROTOS, _DRAW_PROTOS, _JOIN_PROTOS,
-                  _SUMS_PROTOS, _JOIN_SELECT_PROTOS)
+                  _SUMS_PROTOS, _JOIN_SELECT_PROTOS, _NEAR_PROTOS)
         for name, (res, args) in [item for table in tables for item in table.items()]:
             fn = getattr(handle, name)
             fn.restype = res

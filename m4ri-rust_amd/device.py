@@ -197,6 +197,19 @@ class DMat:
         out = join_select(self, other, c0, b, wcols, wlo, whi)
         return (out[0],) + out[3:]
 
+    def near_pairs(self, other, wcols, wlo, whi, flags=0):
+        """The pairs of a row of self and a row of `other` whose XOR has between wlo and whi ones in the columns wcols = (wc0, wc1)
+        (None: all), as a new DMat of exactly `hits` rows ordered by (row of self, row of other) (include/m4ri_hip_near.h; flags:
+        NEAR_OFF_DIAGONAL, NEAR_UPPER) -> (D, ia, ib, wt): the rows and the distance of every hit, on the device (.ptr, .read(stream))."""
+        out = near_pairs(self, other, wcols, wlo, whi, flags=flags)
+        return (out[0],) + out[2:]
+
+    def nearest(self, other, wcols=None, flags=0):
+        """For every row of self the lowest nearest row of `other` on the columns wcols and its distance (-1, -1 where `flags` admit
+        none), as two numpy int32 arrays (include/m4ri_hip_near.h)."""
+        idx, dist = nearest(self, other, wcols, flags=flags)
+        return idx.read(None), dist.read(None)
+
     def subset_sums(self, p, base=None):
         """All C(nrows, p) XORs of p rows of self (each ^ base, a 1-row DMat, if given) as a new DMat, in the colexicographic order of
         the subsets: row C(c_1, 1) + ... + C(c_p, p) is the sum of the rows c_1 < ... < c_p (include/m4ri_hip_sums.h)."""
@@ -779,6 +792,79 @@ def join_select(A, B, c0, b, wcols, wlo, whi, D=None, cap=None, store=True, coun
         if own:
             own.mat._streams.add(stream)
     return (D if store else None, own_c, own_h) + tuple(owned)
+
+
+NEAR_OFF_DIAGONAL = 1  # flags of near_pairs / nearest: pairs with ia == ib are not admitted (A is B: a row is not its own neighbour)
+NEAR_UPPER = 2         # only pairs with ia < ib are admitted (A is B: every unordered pair once)
+
+
+def near_plan(nrows_a, nrows_b, ncols, wcols=None):
+    """How the Hamming-distance search runs (include/m4ri_hip_near.h, no device needed) -> (kernel: the words of the range wcols that
+    it keeps in registers per row of A, 1, 2, 4, 8 or 16, and 0 for the wide kernel; threads per workgroup; rows of A per workgroup;
+    the chunks S that B is cut into; rows of B per chunk; LDS bytes; scratch bytes; the words of a row that hold a column of the
+    range); None for a bad shape or range."""
+    wc0, wc1 = (0, ncols) if wcols is None else wcols
+    out = (ctypes.c_longlong * 8)()
+    v = _lib.lib().gf2_near_plan(nrows_a, nrows_b, ncols, wc0, wc1, out)
+    return None if v < 0 else tuple(int(x) for x in out)
+
+
+def near_pairs(A, B, wcols, wlo, whi, flags=0, D=None, cap=None, store=True, hits=None, ia=None, ib=None, wt=None, stream=None):
+    """The pairs of a row of A and a row of B that are close (include/m4ri_hip_near.h): of all pairs (ia, ib) that `flags` admits
+    (NEAR_OFF_DIAGONAL: not ia == ib; NEAR_UPPER: only ia < ib), ordered by (ia, ib), only the HITS -- those whose XOR has between wlo
+    and whi ones in the columns wcols = (wc0, wc1) (None: all columns) -- are written.  -> (D, hits, ia, ib, wt), all on the device:
+    D[h], ia[h], ib[h], wt[h] for the h-th hit and `hits`, an int64, the number of all hits, which may exceed the capacity.  The
+    arrays follow join_select(): a raw device address (None is returned in its place), None (the wrapper allocates the array and
+    returns an object with .ptr and .read(stream)), and for ia / ib / wt SKIP (0): not wanted.  The capacity is D.nrows, else `cap`;
+    the call then only enqueues on `stream`.  With neither, a counts-only call comes first, the wrapper WAITS for it and sizes D to
+    exactly `hits` rows.  store=False: the rows are not stored -- D is passed without data, None is returned in its place and only
+    ia, ib and wt are written (the index-only mode).  A may be B."""
+    L = _lib.lib()
+    wc0, wc1 = (0, A.ncols) if wcols is None else wcols
+    own_h = _Int64Scratch() if hits is None else None
+    hptr = own_h.ptr if own_h else hits
+
+    def call(Dm, pa, pb, pw):
+        rc = L.gf2_near_pairs_dev(Dm._on(stream), A._on(stream), B._on(stream), wc0, wc1, wlo, whi, flags, hptr, pa, pb, pw, stream)
+        _lib.check(rc, "gf2_near_pairs_dev")
+
+    if D is not None and not store:
+        raise ValueError("near_pairs: store=False takes no D")
+    if D is None:
+        if cap is None:
+            if own_h is None:
+                raise ValueError("near_pairs: a raw hits address needs D or cap (the wrapper cannot read the hits to size D)")
+            call(DMat.wrap(None, 0, A.ncols, A.ld), None, None, None)
+            cap = int(own_h.read(stream)[0])
+            if cap >= 1 << 31:
+                raise ValueError("near_pairs: %d hits do not fit a matrix; give D or cap" % cap)
+        D = DMat(cap, A.ncols) if store else DMat.wrap(None, cap, A.ncols, max((A.ncols + 63) // 64, 1))
+    owned = [_IntScratch(D.nrows) if given is None and D.nrows > 0 else None for given in (ia, ib, wt)]
+    ptrs = [own.ptr if own else (given or None) for own, given in zip(owned, (ia, ib, wt))]
+    call(D, *ptrs)
+    for own in [own_h] + owned:
+        if own:
+            own.mat._streams.add(stream)
+    return (D if store else None, own_h) + tuple(owned)
+
+
+def nearest(A, B, wcols=None, flags=0, idx=None, dist=None, stream=None):
+    """For every row of A the nearest row of B on the columns wcols = (wc0, wc1) (None: all columns) among those that `flags` admits
+    (include/m4ri_hip_near.h) -> (idx, dist): idx[i] the lowest such row, dist[i] its distance, both -1 where no row is admitted.
+    Each is a raw device address of A.nrows int32 (None is returned in its place), None (the wrapper allocates the array and returns
+    an object with .ptr and .read(stream)) or SKIP (0): not wanted (not both).  The call only enqueues on `stream`."""
+    wc0, wc1 = (0, A.ncols) if wcols is None else wcols
+    owned = [_IntScratch(max(A.nrows, 1)) if given is None else None for given in (idx, dist)]
+    for own in owned:
+        if own:
+            own.count = A.nrows
+    ptrs = [own.ptr if own else (given or None) for own, given in zip(owned, (idx, dist))]
+    rc = _lib.lib().gf2_nearest_dev(A._on(stream), B._on(stream), wc0, wc1, flags, ptrs[0], ptrs[1], stream)
+    _lib.check(rc, "gf2_nearest_dev")
+    for own in owned:
+        if own:
+            own.mat._streams.add(stream)
+    return tuple(owned)
 
 
 def subset_count(n, p):
