@@ -14,26 +14,6 @@
 
 namespace {
 
-// the checks of the window that the two entries share
-int check_window(const char *fn, gf2_dmat const *P, int c0, int b) {
-  if (b < 0 || b > kLf1MaxB) return gf2_bad_arg(fn, "b = " + std::to_string(b) + " is outside 0 <= b <= " + std::to_string(kLf1MaxB));
-  if (c0 < 0 || (long long)c0 + b > P->ncols)
-    return gf2_bad_arg(fn, "the columns [c0, c0 + b) = [" + std::to_string(c0) + ", " + std::to_string((long long)c0 + b) +
-                               ") are outside P (" + std::to_string(P->ncols) + " columns)");
-  return 0;
-}
-
-struct IntArray {
-  const char *name;
-  const void *p;
-  long long bytes;
-};
-
-int refuse_array_meets_mat(const char *fn, const IntArray &a, const char *m, gf2_dmat const *M) {
-  if (!a.p || !gf2_range_meets_mat(a.p, a.bytes, M)) return 0;
-  return gf2_bad_arg(fn, std::string(a.name) + " and " + m + " overlap: the address range of " + a.name + " may not meet " + m + "'s");
-}
-
 // first <- all-ones bytes, then the minima; behind this the table is final on `s`
 int enqueue_first(const char *fn, gf2_dmat const *P, int c0, int b, int *first, hipStream_t s) {
   GF2_RC(gf2_hip_rc(hipMemsetAsync(first, 0xFF, (size_t)4 << b, s), fn));  // the workgroups lower it behind this, on the same stream
@@ -46,10 +26,11 @@ int enqueue_first(const char *fn, gf2_dmat const *P, int c0, int b, int *first, 
 extern "C" int gf2_class_first_dev(gf2_dmat const *P, int c0, int b, int *first, void *stream) {
   static const char fn[] = "gf2_class_first_dev";
   if (gf2_check_mat(fn, "P", P)) return -1;
-  GF2_RC(check_window(fn, P, c0, b));
+  GF2_RC(gf2_check_key_window(fn, "P", P->ncols, c0, b, kLf1MaxB));
   GF2_RC(gf2_check_ptr(fn, "first", first, 4));
-  const IntArray f = {"first", first, 4ll << b};
-  GF2_RC(refuse_array_meets_mat(fn, f, "P", P));
+  const Gf2FlatArray f = {"first", first, 4ll << b};
+  const Gf2NamedMat mat = {"P", P};
+  GF2_RC(gf2_refuse_array_overlaps(fn, &f, 1, &mat, 1));
   GF2_RC(gf2_require_device_for(fn));
   return enqueue_first(fn, P, c0, b, first, static_cast<hipStream_t>(stream));
 }
@@ -59,7 +40,7 @@ extern "C" int gf2_lf1_reduce_dev(gf2_dmat *D, gf2_dmat const *P, int c0, int b,
   if (gf2_check_mat(fn, "P", P)) return -1;
   if (gf2_check_mat(fn, "D", D)) return -1;
   if (D->nrows > 0) GF2_RC(gf2_refuse_null(fn, "D.data", D->data));  // also where a row has no word
-  GF2_RC(check_window(fn, P, c0, b));
+  GF2_RC(gf2_check_key_window(fn, "P", P->ncols, c0, b, kLf1MaxB));
   if (flags & ~GF2_LF1_KEEP_ZERO) return gf2_bad_arg(fn, "flags = " + std::to_string(flags) + " has bits other than GF2_LF1_KEEP_ZERO");
   if (D->ncols != P->ncols)
     return gf2_bad_arg(fn, "D has " + std::to_string(D->ncols) + " columns, P " + std::to_string(P->ncols) + ": D->ncols must equal P->ncols");
@@ -68,14 +49,9 @@ extern "C" int gf2_lf1_reduce_dev(gf2_dmat *D, gf2_dmat const *P, int c0, int b,
   GF2_RC(gf2_refuse_misaligned(fn, "src", src, 4));
   // aliasing, last
   GF2_RC(gf2_refuse_overlap(fn, "D", D, "P", P));
-  const IntArray arrays[3] = {{"first", first, 4ll << b}, {"count", count, 4}, {"src", src, 4ll * D->nrows}};
-  for (int i = 0; i < 3; ++i) {
-    GF2_RC(refuse_array_meets_mat(fn, arrays[i], "P", P));
-    GF2_RC(refuse_array_meets_mat(fn, arrays[i], "D", D));
-    for (int j = 0; j < i; ++j)
-      if (arrays[i].p && gf2_ranges_meet(arrays[i].p, arrays[i].bytes, arrays[j].p, arrays[j].bytes))
-        return gf2_bad_arg(fn, std::string(arrays[j].name) + " and " + arrays[i].name + " overlap: their address ranges may not meet");
-  }
+  const Gf2FlatArray arrays[3] = {{"first", first, 4ll << b}, {"count", count, 4}, {"src", src, 4ll * D->nrows}};
+  const Gf2NamedMat mats[2] = {{"P", P}, {"D", D}};
+  GF2_RC(gf2_refuse_array_overlaps(fn, arrays, 3, mats, 2));
   GF2_RC(gf2_require_device_for(fn));
   hipStream_t s = static_cast<hipStream_t>(stream);
   GF2_RC(enqueue_first(fn, P, c0, b, first, s));

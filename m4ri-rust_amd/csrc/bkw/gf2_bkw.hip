@@ -6,8 +6,9 @@
 //   scan:          block counts -> offsets, *count                gf2_lf1_scan_kernel
 //   scatter:       D[offset + rank] = P[i] ^ P[first[key(i)]]     gf2_lf1_scatter_kernel<1 | 2 | 8 | 64 lanes per row, rows per lane>
 //
-// The key of a row is read by lf1_key alone.  A minimum of row indices does not depend on the order in which the rows arrive, the
-// ranks come from ballots and integer sums, and every row of D has one writer: the results are the same bits in every run.
+// The key of a row is read by gf2_row_key (gf2_dev_words.h) alone.  A minimum of row indices does not depend on the order in which
+// the rows arrive, the ranks come from ballots and integer sums, and every row of D has one writer: the results are the same bits in
+// every run.
 //
 // THE TABLE.  `first` is preset to all-ones bytes by the caller (a memset on the stream), which is above every row index as an
 // unsigned value and reads -1 as an int: an empty class needs no pass of its own.  A table entry only ever decreases, so a row that
@@ -19,43 +20,12 @@
 // segments' counts go through LDS once and every lane sums the ones before its own.
 #include <hip/hip_runtime.h>
 
+#include "../gf2_dev_words.h"
 #include "../gf2_kernels.h"
 #include "bkw_plan.h"
 #include "gf2_bkw.h"
 
-typedef uint64_t u64;
-typedef uint32_t u32;
-
 namespace {
-
-// where the key lies in a row: word w0 from bit s on, `two`: the window runs on into word w0 + 1 (then s > 0)
-struct Lf1Window {
-  int w0, s, b;
-  bool two;
-  u32 mask;
-};
-
-__device__ __forceinline__ Lf1Window lf1_window(int c0, int b) {
-  Lf1Window w;
-  w.w0 = c0 >> 6;
-  w.s = c0 & 63;
-  w.b = b;
-  w.two = w.s + b > 64;
-  w.mask = (1u << b) - 1;
-  return w;
-}
-
-// bits [c0, c0 + b) of a row: one word, or two funnelled together when the window crosses a word boundary (b <= 30: never three);
-// the second word is read only then, and no word at all for b == 0
-__device__ __forceinline__ u32 lf1_key(const u64 *row, Lf1Window w) {
-  u32 v = 0;
-  if (w.b > 0) {
-    u64 x = row[w.w0] >> w.s;
-    if (w.two) x |= row[w.w0 + 1] << (64 - w.s);
-    v = (u32)x & w.mask;
-  }
-  return v;
-}
 
 // ---- class firsts: rows by a grid-stride loop, a lane per row
 
@@ -68,9 +38,9 @@ __global__ void __launch_bounds__(kLf1FirstThreads) gf2_lf1_first_kernel(const u
     for (u32 i = threadIdx.x; i < size; i += kLf1FirstThreads) lf1_table[i] = ~0u;
     __syncthreads();
   }
-  const Lf1Window w = lf1_window(c0, b);
+  const Gf2KeyWindow w = gf2_key_window(c0, b);
   for (long long r = (long long)blockIdx.x * kLf1FirstThreads + threadIdx.x; r < nrows; r += (long long)gridDim.x * kLf1FirstThreads) {
-    const u32 v = lf1_key(P + r * ld, w);
+    const u32 v = gf2_row_key(P + r * ld, w);
     // the result of the atomic is not used: the no-return form
     if (LDS) {
       if (__atomic_load_n(&lf1_table[v], __ATOMIC_RELAXED) > (u32)r) atomicMin(&lf1_table[v], (u32)r);
@@ -94,11 +64,11 @@ struct Lf1Row {
   int partner;  // the row to XOR in, -1: none (a kept row of key 0)
 };
 
-__device__ __forceinline__ Lf1Row lf1_row(const u64 *P, long long ld, long long r, long long nrows, Lf1Window w, int keep_zero,
+__device__ __forceinline__ Lf1Row lf1_row(const u64 *P, long long ld, long long r, long long nrows, Gf2KeyWindow w, int keep_zero,
                                            const int *first) {
   Lf1Row o = {false, -1};
   if (r < nrows) {
-    const u32 v = lf1_key(P + r * ld, w);
+    const u32 v = gf2_row_key(P + r * ld, w);
     const int f = first[v];
     if (keep_zero && v == 0)
       o.survives = true;
@@ -137,7 +107,7 @@ template <int ITEMS>
 __global__ void __launch_bounds__(kLf1Threads) gf2_lf1_count_kernel(const u64 *P, long long ld, long long nrows, int c0, int b, int keep_zero,
                                                                     const int *first, int *counts) {
   __shared__ int seg[ITEMS * (kLf1Threads / 64)];
-  const Lf1Window w = lf1_window(c0, b);
+  const Gf2KeyWindow w = gf2_key_window(c0, b);
   const long long base = (long long)blockIdx.x * (kLf1Threads * ITEMS) + threadIdx.x;
   bool m[ITEMS];
   int rank[ITEMS], total;
@@ -161,6 +131,7 @@ __global__ void __launch_bounds__(kLf1Threads) gf2_lf1_scan_kernel(int *counts, 
       v[i] = k0 + i < nblk ? counts[k0 + i] : 0;
       mine += v[i];
     }
+    // the wave scan written out, not gf2_block_scan: with the call this kernel compiles to other code (25 -> 28 VGPRs)
     int incl = mine;  // inclusive sums over the wave
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -188,8 +159,6 @@ __global__ void __launch_bounds__(kLf1Threads) gf2_lf1_scan_kernel(int *counts, 
 
 // ---- scatter
 
-__device__ __forceinline__ u64 lf1_lo_hi(u32 lo, u32 hi) { return (u64)lo | ((u64)hi << 32); }
-
 // d = a ^ p (p null: d = a) over the nw words of a row, the last one masked; lane `sub` of LANES takes the pairs of words sub,
 // sub + LANES, ...  vec_p / vec_d: the rows of P / of D start on 16-byte boundaries, so a pair is one 16-byte access; an odd last word
 // goes alone either way
@@ -203,12 +172,12 @@ __device__ __forceinline__ void lf1_xor_row(u64 *d, const u64 *a, const u64 *p, 
       u64 x0, x1;
       if (vec_p) {
         const uint4 x = *reinterpret_cast<const uint4 *>(a + k);
-        x0 = lf1_lo_hi(x.x, x.y);
-        x1 = lf1_lo_hi(x.z, x.w);
+        x0 = gf2_lo_hi(x.x, x.y);
+        x1 = gf2_lo_hi(x.z, x.w);
         if (p) {
           const uint4 y = *reinterpret_cast<const uint4 *>(p + k);
-          x0 ^= lf1_lo_hi(y.x, y.y);
-          x1 ^= lf1_lo_hi(y.z, y.w);
+          x0 ^= gf2_lo_hi(y.x, y.y);
+          x1 ^= gf2_lo_hi(y.z, y.w);
         }
       } else {
         x0 = a[k];
@@ -243,7 +212,7 @@ __global__ void __launch_bounds__(kLf1Threads) gf2_lf1_scatter_kernel(const u64 
   constexpr int RUN = kLf1Threads * ITEMS;
   __shared__ int seg[ITEMS * (kLf1Threads / 64)];
   __shared__ int dest[LANES == 1 ? 1 : RUN], mate[LANES == 1 ? 1 : RUN];
-  const Lf1Window w = lf1_window(c0, b);
+  const Gf2KeyWindow w = gf2_key_window(c0, b);
   const long long nw = ((long long)ncols + 63) >> 6;
   const u64 mlast = ~0ull >> (63 - (int)(((long long)ncols - 1) & 63));
   const long long run0 = (long long)blockIdx.x * RUN;
@@ -282,11 +251,6 @@ __global__ void __launch_bounds__(kLf1Threads) gf2_lf1_scatter_kernel(const u64 
       lf1_xor_row<LANES>(D + (long long)to * ldd, P + (run0 + q) * ld, f >= 0 ? P + (long long)f * ld : nullptr, nw, mlast, vec_p, vec_d, sub);
     }
   }
-}
-
-// 16-byte accesses only where every row starts on a 16-byte boundary and a row has a pair of words
-int lf1_rows_aligned16(const u64 *A, long long ld, long long nrows, long long nw) {
-  return nw > 1 && !(reinterpret_cast<uintptr_t>(A) & 15) && (!(ld & 1) || nrows == 1);
 }
 
 }  // namespace
@@ -334,7 +298,7 @@ extern "C" hipError_t gf2k_lf1_scatter(const u64 *P, long long ld, int nrows, in
   const bool narrow = plan.rows == kLf1Threads * kLf1NarrowItems;
   if (lanes < 0) lanes = plan.lanes;
   const long long nw = ((long long)ncols + 63) >> 6;
-  const int vec_p = lf1_rows_aligned16(P, ld, nrows, nw), vec_d = lf1_rows_aligned16(D, ldd, cap, nw);
+  const int vec_p = gf2_rows_aligned16(P, ld, nrows, nw), vec_d = gf2_rows_aligned16(D, ldd, cap, nw);
   const dim3 grid((unsigned)plan.blocks), block(kLf1Threads);
   if (narrow && lanes == 1)
     LF1_SCATTER(1, kLf1NarrowItems);

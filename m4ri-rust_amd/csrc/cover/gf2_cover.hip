@@ -23,12 +23,10 @@
 #include <set>
 #include <utility>
 
+#include "../gf2_dev_words.h"
 #include "../gf2_kernels.h"
 #include "cover_plan.h"
 #include "gf2_cover.h"
-
-typedef uint64_t u64;
-typedef uint32_t u32;
 
 namespace {
 
@@ -221,8 +219,7 @@ extern "C" hipError_t gf2k_cover_reduce(const u64 *P, long long ld, int nrows, i
     words += 1 << (codes[c].n - codes[c].k);
   }
   const int nwd = (int)((plan.K + 63) >> 6);
-  // 16-byte stores only where every row of D starts on a 16-byte boundary and has a pair of words
-  const int vec_d = nwd > 1 && !(reinterpret_cast<uintptr_t>(D) & 15) && (!(ldd & 1) || nrows == 1);
+  const int vec_d = gf2_rows_aligned16(D, ldd, nrows, nwd);
   const int stride = plan.span | 1;
   int lanes_log2 = 0;
   while ((1 << lanes_log2) < plan.span) ++lanes_log2;

@@ -122,6 +122,45 @@ static inline int gf2_refuse_array_overlaps(const char *fn, const Gf2FlatArray *
   }
   return 0;
 }
+// ---- the rules that the LPN entries share (bkw, lf2, join, near, sums): one text each
+
+// the key window [c0, c0 + b) of a call: its width, then its place in a matrix of ncols columns that the message calls `what` ("P",
+// "A and B").  An entry with a check of its own between the two (gf2_join_dev) calls the halves in its own order
+static inline int gf2_check_key_bits(const char *fn, int b, int maxb) {
+  if (b < 0 || b > maxb) return gf2_bad_arg(fn, "b = " + std::to_string(b) + " is outside 0 <= b <= " + std::to_string(maxb));
+  return 0;
+}
+static inline int gf2_check_key_columns(const char *fn, const char *what, int ncols, int c0, int b) {
+  if (c0 < 0 || (long long)c0 + b > ncols)
+    return gf2_bad_arg(fn, "the columns [c0, c0 + b) = [" + std::to_string(c0) + ", " + std::to_string((long long)c0 + b) + ") are outside " +
+                               what + " (" + std::to_string(ncols) + " columns)");
+  return 0;
+}
+static inline int gf2_check_key_window(const char *fn, const char *what, int ncols, int c0, int b, int maxb) {
+  GF2_RC(gf2_check_key_bits(fn, b, maxb));
+  return gf2_check_key_columns(fn, what, ncols, c0, b);
+}
+// the columns [wc0, wc1) whose ones are counted, in a matrix of ncols columns
+static inline int gf2_check_weight_range(const char *fn, int ncols, int wc0, int wc1) {
+  if (wc0 < 0 || wc0 > wc1 || wc1 > ncols)
+    return gf2_bad_arg(fn, "the weight range [wc0, wc1) = [" + std::to_string(wc0) + ", " + std::to_string(wc1) + ") is outside 0 <= wc0 <= wc1 <= " +
+                               std::to_string(ncols) + " columns");
+  return 0;
+}
+// the weights [wlo, whi] that make a pair a hit
+static inline int gf2_check_weight_window(const char *fn, int wlo, int whi) {
+  if (wlo < 0 || wlo > whi)
+    return gf2_bad_arg(fn, "the weight window [wlo, whi] = [" + std::to_string(wlo) + ", " + std::to_string(whi) + "] is outside 0 <= wlo <= whi");
+  return 0;
+}
+// two pools and the matrix of their XORs: one width
+static inline int gf2_check_equal_ncols(const char *fn, gf2_dmat const *A, gf2_dmat const *B, gf2_dmat const *D) {
+  if (B->ncols != A->ncols || D->ncols != A->ncols)
+    return gf2_bad_arg(fn, "A has " + std::to_string(A->ncols) + " columns, B " + std::to_string(B->ncols) + ", D " + std::to_string(D->ncols) +
+                               ": A->ncols, B->ncols and D->ncols must be equal");
+  return 0;
+}
+
 // two matrices by address range, whatever their strides (gf2_inverse_batch_dev: its kernel owns whole stacks)
 static inline bool gf2_mat_ranges_meet(gf2_dmat const *X, gf2_dmat const *Y) {
   if (X->nrows <= 0 || X->ncols <= 0 || Y->nrows <= 0 || Y->ncols <= 0) return false;

@@ -93,16 +93,14 @@ extern "C" int gf2_draw_permutation_dev(int *perm, int n, uint64_t seed, void *s
   std::lock_guard<std::mutex> lk(gf2_enqueue_mu);  // another thread on the same stream would be handed the same scratch
   void *scratch = nullptr;
   GF2_RC(gf2_stream_scratch(s, (size_t)plan.sort_scratch, &scratch, GF2_SLOT_DRAW_PERM));
-  char *base = static_cast<char *>(scratch);
-  void *pairs[2] = {base, base + plan.pair_bytes};
-  int *counts = reinterpret_cast<int *>(base + 2 * plan.pair_bytes);
-  int *parts = reinterpret_cast<int *>(base + 2 * plan.pair_bytes + plan.count_bytes);
-  GF2_RC(gf2_hip_rc(gf2k_draw_perm_pairs(pairs[0], n, seed, s), fn));
-  // the class sort on pairs from pass 0 on: no matrix, the pairs go from one buffer to the other and the last pass writes perm
+  const Lf2SortWork w = lf2_sort_work(scratch, plan);
+  GF2_RC(gf2_hip_rc(gf2k_draw_perm_pairs(w.pairs[0], n, seed, s), fn));
+  // the class sort on pairs from pass 0 on, not gf2_enqueue_class_sort: no matrix, the pairs go from one buffer to the other and the
+  // last pass writes perm
   for (int pass = 0; pass < plan.passes; ++pass) {
     const bool last = pass == plan.passes - 1;
-    const hipError_t e = gf2k_lf2_sort_pass(nullptr, 0, 0, kDrawPermKeyBits, pairs[pass & 1], n, pass, counts, parts,
-                                            last ? nullptr : pairs[(pass + 1) & 1], last ? perm : nullptr, nullptr, s);
+    const hipError_t e = gf2k_lf2_sort_pass(nullptr, 0, 0, kDrawPermKeyBits, w.pairs[pass & 1], n, pass, w.counts, w.parts,
+                                            last ? nullptr : w.pairs[(pass + 1) & 1], last ? perm : nullptr, nullptr, s);
     GF2_RC(gf2_hip_rc(e, fn));
   }
   return 0;

@@ -10,13 +10,11 @@
 // and the only atomic adds integers: two runs give the same bits.
 #include <hip/hip_runtime.h>
 
+#include "../gf2_dev_words.h"
 #include "../gf2_kernels.h"
 #include "draw_plan.h"
 #include "gf2_draw.h"
 #include "philox.h"
-
-typedef uint64_t u64;
-typedef uint32_t u32;
 
 namespace {
 
@@ -194,8 +192,7 @@ extern "C" hipError_t gf2k_bernoulli(u64 *D, long long ld, int rows, int cols, u
   if (rows <= 0 || cols <= 0 || thr == 0) return hipErrorInvalidValue;
   const long long w = ((long long)cols + 63) >> 6;
   const u64 mlast = ~0ull >> (63 - (int)(((long long)cols - 1) & 63));
-  // 16-byte accesses only where every row starts on a 16-byte boundary and a row has a pair of words
-  const bool vec = w > 1 && !(reinterpret_cast<uintptr_t>(D) & 15) && (!(ld & 1) || rows == 1);
+  const bool vec = gf2_rows_aligned16(D, ld, rows, w);
   if (vec)
     DRAW_BERNOULLI(2, (long long)rows * ((w + 1) >> 1));
   else

@@ -30,16 +30,12 @@
 #include <set>
 #include <utility>
 
+#include "../gf2_dev_words.h"
 #include "../gf2_kernels.h"
 #include "gather_plan.h"
 #include "gf2_gather.h"
 
-typedef uint64_t u64;
-typedef uint32_t u32;
-
 namespace {
-
-__device__ __forceinline__ u64 gather_lo_hi(u32 lo, u32 hi) { return (u64)lo | ((u64)hi << 32); }
 
 // blockDim = (pieces, rows), 256 threads; rows walk grid.x, the pieces of a row grid.y, both with a stride loop.  A piece is a 16-byte
 // pair of words when vec (every row of D and S starts on a 16-byte boundary: the launcher decides), else one word; the last word of a
@@ -62,15 +58,15 @@ __global__ void __launch_bounds__(256) gf2_gather_rows_kernel(u64 *D, long long 
         u64 v0 = 0, v1 = 0;
         if (ok) {
           const uint4 x = *reinterpret_cast<const uint4 *>(s + k);
-          v0 = gather_lo_hi(x.x, x.y);
-          v1 = gather_lo_hi(x.z, x.w);
+          v0 = gf2_lo_hi(x.x, x.y);
+          v1 = gf2_lo_hi(x.z, x.w);
         }
         if (k + 1 == nw - 1) v1 &= mlast;
         uint4 *p = reinterpret_cast<uint4 *>(d + k);
         if (accumulate) {
           const uint4 o = *p;
-          v0 ^= gather_lo_hi(o.x, o.y);
-          v1 ^= gather_lo_hi(o.z, o.w);
+          v0 ^= gf2_lo_hi(o.x, o.y);
+          v1 ^= gf2_lo_hi(o.z, o.w);
         }
         *p = make_uint4((u32)v0, (u32)(v0 >> 32), (u32)v1, (u32)(v1 >> 32));
       } else {
@@ -181,9 +177,7 @@ extern "C" hipError_t gf2k_gather_rows(u64 *D, long long ldd, const u64 *S, long
   if (d_nrows <= 0 || ncols <= 0) return hipSuccess;
   const long long nw = ((long long)ncols + 63) >> 6;
   // 16-byte pieces only where every row of both matrices starts on a 16-byte boundary (an empty S is never read)
-  const bool s16 = s_nrows <= 0 || (!(reinterpret_cast<uintptr_t>(S) & 15) && (!(lds_ & 1) || s_nrows == 1));
-  const bool d16 = !(reinterpret_cast<uintptr_t>(D) & 15) && (!(ldd & 1) || d_nrows == 1);
-  const int vec = s16 && d16 && nw > 1;
+  const int vec = (s_nrows <= 0 || gf2_rows_aligned16(S, lds_, s_nrows, nw)) && gf2_rows_aligned16(D, ldd, d_nrows, nw);
   const long long units = vec ? (nw + 1) >> 1 : nw;
   int wx = 1;  // pieces across a workgroup: the power of two that covers a row, 256 at the most
   while (wx < units && wx < 256) wx <<= 1;

@@ -14,12 +14,10 @@
 // Everything is integer arithmetic with one writer per output word and no atomics: two runs give the same bits.
 #include <hip/hip_runtime.h>
 
+#include "../gf2_dev_words.h"
 #include "../gf2_kernels.h"
 #include "gf2_join.h"
 #include "join_plan.h"
-
-typedef uint64_t u64;
-typedef uint32_t u32;
 
 namespace {
 
@@ -49,54 +47,7 @@ __device__ __forceinline__ long long join_upper_bound(const int *keys, long long
   return lo;
 }
 
-// the position of output j of a run: the largest q < n with pre[q] <= j, where pre[q] = the outputs of the positions before q
-// (pre[0] == 0 <= j < the run's total).  Positions without outputs (pre[q] == pre[q + 1]) are never the answer.
-__device__ __forceinline__ int join_find_position(const long long *pre, int n, long long j) {
-  int lo = 0, hi = n;  // pre[lo] <= j, and hi == n or pre[hi] > j
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (pre[mid] <= j)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
-// the ones of word k of a row, value x, that lie in the columns [wc0, wc1): the first and the last word of the range are masked, a
-// word outside it counts nothing
-__device__ __forceinline__ int join_word_weight(u64 x, long long k, int wc0, int wc1) {
-  const long long lo = 64 * k, hi = lo + 64;
-  if (wc0 >= wc1 || wc1 <= lo || wc0 >= hi) return 0;
-  u64 m = ~0ull;
-  if (wc0 > lo) m &= ~0ull << (wc0 - lo);
-  if (wc1 < hi) m &= ~0ull >> (hi - wc1);
-  return __popcll(x & m);
-}
-
-// ---- sums over a workgroup
-
-// the sum of `mine` over the lanes before this one, and (in *total) over all.  Every lane calls it; a barrier lies inside, and the
-// caller puts one before wave_sum is used again.
-__device__ __forceinline__ long long join_block_scan(long long mine, long long *wave_sum, long long *total) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  long long incl = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const long long o = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += o;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  long long before = incl - mine, all = 0;
-#pragma unroll
-  for (int wv = 0; wv < kJoinWaves; ++wv) {
-    if (wv < wave) before += wave_sum[wv];
-    all += wave_sum[wv];
-  }
-  *total = all;
-  return before;
-}
+// ---- sums over a workgroup (gf2_block_scan)
 
 // one workgroup: v[k] becomes the sum of the values before k, *total the sum of all
 __global__ void __launch_bounds__(kJoinThreads) gf2_join_scan_kernel(long long *v, long long n, long long *total) {
@@ -110,7 +61,7 @@ __global__ void __launch_bounds__(kJoinThreads) gf2_join_scan_kernel(long long *
       x[i] = k0 + i < n ? v[k0 + i] : 0;
       mine += x[i];
     }
-    long long before = running + join_block_scan(mine, wave_sum, &all);
+    long long before = running + gf2_block_scan<long long, kJoinWaves>(mine, wave_sum, &all);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (k0 + i < n) v[k0 + i] = before;
@@ -181,26 +132,12 @@ __global__ void __launch_bounds__(kJoinThreads) gf2_join_count_kernel(const int 
   long long mine = 0, total;
 #pragma unroll
   for (int i = 0; i < kJoinRunItems; ++i) mine += c[i];
-  join_block_scan(mine, wave_sum, &total);
+  gf2_block_scan<long long, kJoinWaves>(mine, wave_sum, &total);
   if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 
-__device__ __forceinline__ u64 join_lo_hi(u32 lo, u32 hi) { return (u64)lo | ((u64)hi << 32); }
-
-// two words of a row from word k on; vec: the rows of this operand start on 16-byte boundaries, so the pair is one 16-byte access
-__device__ __forceinline__ void join_load2(const u64 *row, long long k, int vec, u64 &x0, u64 &x1) {
-  if (vec) {
-    const uint4 x = *reinterpret_cast<const uint4 *>(row + k);
-    x0 = join_lo_hi(x.x, x.y);
-    x1 = join_lo_hi(x.z, x.w);
-  } else {
-    x0 = row[k];
-    x1 = row[k + 1];
-  }
-}
-
 // d = a ^ p over the nw words of a row, the last one masked; lane `sub` of LANES takes the pairs of words sub, sub + LANES, ...
-// -> the ones of this lane's words of d in the columns [wc0, wc1).  vec_a / vec_b / vec_d: see join_load2; an odd last word goes alone
+// -> the ones of this lane's words of d in the columns [wc0, wc1).  vec_a / vec_b / vec_d: see gf2_load2; an odd last word goes alone
 template <int LANES>
 __device__ __forceinline__ int join_xor_row(u64 *d, const u64 *a, const u64 *p, long long nw, u64 mlast, int vec_a, int vec_b, int vec_d,
                                             int sub, int wc0, int wc1) {
@@ -211,12 +148,12 @@ __device__ __forceinline__ int join_xor_row(u64 *d, const u64 *a, const u64 *p, 
     const long long k = 2 * u;
     if (k + 1 < nw) {
       u64 x0, x1, y0, y1;
-      join_load2(a, k, vec_a, x0, x1);
-      join_load2(p, k, vec_b, y0, y1);
+      gf2_load2(a, k, vec_a, x0, x1);
+      gf2_load2(p, k, vec_b, y0, y1);
       x0 ^= y0;
       x1 ^= y1;
       if (k + 1 == nw - 1) x1 &= mlast;
-      w += join_word_weight(x0, k, wc0, wc1) + join_word_weight(x1, k + 1, wc0, wc1);
+      w += gf2_word_weight(x0, k, wc0, wc1) + gf2_word_weight(x1, k + 1, wc0, wc1);
       if (vec_d) {
         *reinterpret_cast<uint4 *>(d + k) = make_uint4((u32)x0, (u32)(x0 >> 32), (u32)x1, (u32)(x1 >> 32));
       } else {
@@ -225,7 +162,7 @@ __device__ __forceinline__ int join_xor_row(u64 *d, const u64 *a, const u64 *p, 
       }
     } else {
       const u64 x = (a[k] ^ p[k]) & mlast;
-      w += join_word_weight(x, k, wc0, wc1);
+      w += gf2_word_weight(x, k, wc0, wc1);
       d[k] = x;
     }
   }
@@ -255,7 +192,7 @@ __global__ void __launch_bounds__(kJoinThreads) gf2_join_scatter_kernel(const u6
   long long mine = 0, total;
 #pragma unroll
   for (int i = 0; i < kJoinRunItems; ++i) mine += c[i];
-  long long before = join_block_scan(mine, wave_sum, &total);
+  long long before = gf2_block_scan<long long, kJoinWaves>(mine, wave_sum, &total);
 #pragma unroll
   for (int i = 0; i < kJoinRunItems; ++i) {
     const int q = kJoinRunItems * threadIdx.x + i;
@@ -269,7 +206,7 @@ __global__ void __launch_bounds__(kJoinThreads) gf2_join_scatter_kernel(const u6
   const u64 mlast = ~0ull >> (63 - (int)(((long long)ncols - 1) & 63));
   const int sub = threadIdx.x % LANES;
   for (long long j = threadIdx.x / LANES; j < jmax; j += kJoinThreads / LANES) {  // the lanes of a group share j: they leave together
-    const int q = join_find_position(pre, kJoinRunRows, j);
+    const int q = gf2_find_position(pre, kJoinRunRows, j);
     const long long p = lpos[q] + (j - pre[q]);
     const int a = order_a[s0 + q], r = order_b[p];
     const long long at = off + j;
@@ -282,11 +219,6 @@ __global__ void __launch_bounds__(kJoinThreads) gf2_join_scatter_kernel(const u6
       if (wt) wt[at] = w;
     }
   }
-}
-
-// 16-byte accesses only where every row starts on a 16-byte boundary and a row has a pair of words
-int join_rows_aligned16(const u64 *M, long long ld, long long nrows, long long nw) {
-  return nw > 1 && !(reinterpret_cast<uintptr_t>(M) & 15) && (!(ld & 1) || nrows == 1);
 }
 
 #include "gf2_join_select.inc"  // gf2_join_weigh_kernel / gf2_join_select_scatter_kernel and their launchers: the weight-filtered join
@@ -315,8 +247,8 @@ extern "C" hipError_t gf2k_join_scatter(const u64 *A, long long lda, int nrows_a
   if (plan.passes < 0 || nrows_a <= 0 || nrows_b <= 0 || cap <= 0) return hipErrorInvalidValue;
   if (lanes < 0) lanes = plan.lanes;
   const long long nw = ((long long)ncols + 63) >> 6;
-  const int vec_a = join_rows_aligned16(A, lda, nrows_a, nw), vec_b = join_rows_aligned16(B, ldb, nrows_b, nw),
-            vec_d = join_rows_aligned16(D, ldd, cap, nw);
+  const int vec_a = gf2_rows_aligned16(A, lda, nrows_a, nw), vec_b = gf2_rows_aligned16(B, ldb, nrows_b, nw),
+            vec_d = gf2_rows_aligned16(D, ldd, cap, nw);
   const dim3 grid((unsigned)plan.runs), block(kJoinThreads);
   if (lanes == 1)
     JOIN_SCATTER(1);

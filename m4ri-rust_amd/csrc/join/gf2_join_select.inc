@@ -23,7 +23,7 @@ __device__ __forceinline__ long long join_select_end_word(int wc0, int wc1) { re
 __device__ __forceinline__ int join_select_is_hit(int w, int wlo, int whi) { return w >= wlo && w <= whi; }
 
 // the ones of a ^ p in the columns [wc0, wc1) that lane `sub` of `lanes` counts: the range's words go in pairs (words 2u and 2u + 1, one
-// 16-byte access where the operand allows it: join_load2), pair sub, sub + lanes, ... of the pairs that meet the range.  nw: the words of
+// 16-byte access where the operand allows it: gf2_load2), pair sub, sub + lanes, ... of the pairs that meet the range.  nw: the words of
 // a row; no word from nw on is read, and a word of the row outside the range counts nothing
 __device__ __forceinline__ int join_select_pair_weight(const u64 *a, const u64 *p, long long nw, int vec_a, int vec_b, int sub, int lanes, int wc0,
                                                        int wc1) {
@@ -33,11 +33,11 @@ __device__ __forceinline__ int join_select_pair_weight(const u64 *a, const u64 *
     const long long k = 2 * u;
     if (k + 1 < nw) {
       u64 x0, x1, y0, y1;
-      join_load2(a, k, vec_a, x0, x1);
-      join_load2(p, k, vec_b, y0, y1);
-      w += join_word_weight(x0 ^ y0, k, wc0, wc1) + join_word_weight(x1 ^ y1, k + 1, wc0, wc1);
+      gf2_load2(a, k, vec_a, x0, x1);
+      gf2_load2(p, k, vec_b, y0, y1);
+      w += gf2_word_weight(x0 ^ y0, k, wc0, wc1) + gf2_word_weight(x1 ^ y1, k + 1, wc0, wc1);
     } else {
-      w += join_word_weight(a[k] ^ p[k], k, wc0, wc1);
+      w += gf2_word_weight(a[k] ^ p[k], k, wc0, wc1);
     }
   }
   return w;
@@ -54,7 +54,7 @@ __device__ __forceinline__ long long join_select_run_outputs(const int *ska, lon
   long long mine = 0, total;
 #pragma unroll
   for (int i = 0; i < kJoinRunItems; ++i) mine += c[i];
-  long long before = join_block_scan(mine, wave_sum, &total);
+  long long before = gf2_block_scan<long long, kJoinWaves>(mine, wave_sum, &total);
 #pragma unroll
   for (int i = 0; i < kJoinRunItems; ++i) {
     const int q = kJoinRunItems * threadIdx.x + i;
@@ -83,7 +83,7 @@ __global__ void __launch_bounds__(kJoinThreads) gf2_join_weigh_kernel(const u64 
   const int sub = threadIdx.x % LANES;
   long long mine = 0;
   for (long long j = threadIdx.x / LANES; j < total; j += kJoinThreads / LANES) {  // the lanes of a group share j: they leave together
-    const int q = join_find_position(pre, kJoinRunRows, j);
+    const int q = gf2_find_position(pre, kJoinRunRows, j);
     const long long p = lpos[q] + (j - pre[q]);
     const int a = order_a[s0 + q], r = order_b[p];
     int w = join_select_pair_weight(A + (long long)a * lda, B + (long long)r * ldb, nw, vec_a, vec_b, sub, LANES, wc0, wc1);
@@ -92,7 +92,7 @@ __global__ void __launch_bounds__(kJoinThreads) gf2_join_weigh_kernel(const u64 
     if (sub == 0 && join_select_is_hit(w, wlo, whi)) ++mine;
   }
   long long hits;
-  join_block_scan(mine, wave_sum, &hits);  // wave_sum is free: the scan of the outputs read it before the last barrier of the prologue
+  gf2_block_scan<long long, kJoinWaves>(mine, wave_sum, &hits);  // wave_sum is free: the scan of the outputs read it before the last barrier of the prologue
   if (threadIdx.x == 0) {
     hsums[blockIdx.x] = hits;
     hown[blockIdx.x] = hits;
@@ -130,7 +130,7 @@ __global__ void __launch_bounds__(kJoinThreads) gf2_join_select_scatter_kernel(
     const long long j = j0 + threadIdx.x / LANES;
     int a = 0, r = 0, w = 0;
     if (j < total) {
-      const int q = join_find_position(pre, kJoinRunRows, j);
+      const int q = gf2_find_position(pre, kJoinRunRows, j);
       const long long p = lpos[q] + (j - pre[q]);
       a = order_a[s0 + q];
       r = order_b[p];
@@ -176,7 +176,7 @@ extern "C" hipError_t gf2k_join_weigh(const u64 *A, long long lda, int nrows_a, 
   if (plan.join.passes < 0 || nrows_a <= 0 || nrows_b <= 0) return hipErrorInvalidValue;
   if (lanes < 0) lanes = plan.weigh_lanes;
   const long long nw = ((long long)ncols + 63) >> 6;
-  const int vec_a = join_rows_aligned16(A, lda, nrows_a, nw), vec_b = join_rows_aligned16(B, ldb, nrows_b, nw);
+  const int vec_a = gf2_rows_aligned16(A, lda, nrows_a, nw), vec_b = gf2_rows_aligned16(B, ldb, nrows_b, nw);
   const dim3 grid((unsigned)plan.join.runs), block(kJoinThreads);
   if (lanes == 1)
     JOIN_WEIGH(1);
@@ -205,8 +205,8 @@ extern "C" hipError_t gf2k_join_select_scatter(const u64 *A, long long lda, int 
   if (plan.join.passes < 0 || nrows_a <= 0 || nrows_b <= 0 || cap <= 0) return hipErrorInvalidValue;
   if (lanes < 0) lanes = plan.join.lanes;
   const long long nw = ((long long)ncols + 63) >> 6;
-  const int vec_a = join_rows_aligned16(A, lda, nrows_a, nw), vec_b = join_rows_aligned16(B, ldb, nrows_b, nw),
-            vec_d = D ? join_rows_aligned16(D, ldd, cap, nw) : 0;
+  const int vec_a = gf2_rows_aligned16(A, lda, nrows_a, nw), vec_b = gf2_rows_aligned16(B, ldb, nrows_b, nw),
+            vec_d = D ? gf2_rows_aligned16(D, ldd, cap, nw) : 0;
   const dim3 grid((unsigned)plan.join.runs), block(kJoinThreads);
   if (lanes == 1)
     JOIN_SELECT_SCATTER(1);

@@ -15,27 +15,6 @@
 #include "gf2_join.h"
 #include "join_plan.h"
 
-namespace {
-
-// order and skeys <- the stable sort of M's rows by their key, in the work space `work` (join_plan: sort_bytes).  M->nrows > 0; the
-// caller holds gf2_enqueue_mu.  The sort of lf2/gf2_lf2.hip, the way lf2_host.cpp and draw_host.cpp run it
-int enqueue_sort(const char *fn, gf2_dmat const *M, int c0, int b, char *work, int *order, int *skeys, hipStream_t s) {
-  const Lf2Plan plan = lf2_plan(M->nrows, M->ncols, b);
-  if (plan.passes == 0) return gf2_hip_rc(gf2k_lf2_iota(M->nrows, order, skeys, s), fn);
-  void *pairs[2] = {work, work + plan.pair_bytes};
-  int *counts = reinterpret_cast<int *>(work + 2 * plan.pair_bytes);
-  int *parts = reinterpret_cast<int *>(work + 2 * plan.pair_bytes + plan.count_bytes);
-  for (int pass = 0; pass < plan.passes; ++pass) {
-    const bool first = pass == 0, last = pass == plan.passes - 1;
-    const hipError_t e = gf2k_lf2_sort_pass(first ? M->data : nullptr, M->ld, c0, b, first ? nullptr : pairs[(pass - 1) & 1], M->nrows, pass,
-                                            counts, parts, last ? nullptr : pairs[pass & 1], last ? order : nullptr, last ? skeys : nullptr, s);
-    GF2_RC(gf2_hip_rc(e, fn));
-  }
-  return 0;
-}
-
-}  // namespace
-
 extern "C" int gf2_join_dev(gf2_dmat *D, gf2_dmat const *A, gf2_dmat const *B, int c0, int b, long long *count, int *ia, int *ib, int *wt,
                             int wc0, int wc1, void *stream) {
   static const char fn[] = "gf2_join_dev";
@@ -43,20 +22,14 @@ extern "C" int gf2_join_dev(gf2_dmat *D, gf2_dmat const *A, gf2_dmat const *B, i
   if (gf2_check_mat(fn, "B", B)) return -1;
   if (gf2_check_mat(fn, "D", D)) return -1;
   if (D->nrows > 0) GF2_RC(gf2_refuse_null(fn, "D.data", D->data));  // also where a row has no word
-  if (b < 0 || b > kJoinMaxB) return gf2_bad_arg(fn, "b = " + std::to_string(b) + " is outside 0 <= b <= " + std::to_string(kJoinMaxB));
-  if (B->ncols != A->ncols || D->ncols != A->ncols)
-    return gf2_bad_arg(fn, "A has " + std::to_string(A->ncols) + " columns, B " + std::to_string(B->ncols) + ", D " + std::to_string(D->ncols) +
-                               ": A->ncols, B->ncols and D->ncols must be equal");
-  if (c0 < 0 || (long long)c0 + b > A->ncols)
-    return gf2_bad_arg(fn, "the columns [c0, c0 + b) = [" + std::to_string(c0) + ", " + std::to_string((long long)c0 + b) +
-                               ") are outside A and B (" + std::to_string(A->ncols) + " columns)");
+  GF2_RC(gf2_check_key_bits(fn, b, kJoinMaxB));
+  GF2_RC(gf2_check_equal_ncols(fn, A, B, D));
+  GF2_RC(gf2_check_key_columns(fn, "A and B", A->ncols, c0, b));
   GF2_RC(gf2_check_ptr(fn, "count", count, 8));
   GF2_RC(gf2_refuse_misaligned(fn, "ia", ia, 4));
   GF2_RC(gf2_refuse_misaligned(fn, "ib", ib, 4));
   GF2_RC(gf2_refuse_misaligned(fn, "wt", wt, 4));
-  if (wc0 < 0 || wc0 > wc1 || wc1 > A->ncols)
-    return gf2_bad_arg(fn, "the weight range [wc0, wc1) = [" + std::to_string(wc0) + ", " + std::to_string(wc1) + ") is outside 0 <= wc0 <= wc1 <= " +
-                               std::to_string(A->ncols) + " columns");
+  GF2_RC(gf2_check_weight_range(fn, A->ncols, wc0, wc1));
   // aliasing, last.  A and B are only read: they may overlap or be one view
   GF2_RC(gf2_refuse_overlap(fn, "D", D, "A", A));
   GF2_RC(gf2_refuse_overlap(fn, "D", D, "B", B));
@@ -75,8 +48,8 @@ extern "C" int gf2_join_dev(gf2_dmat *D, gf2_dmat const *A, gf2_dmat const *B, i
   at += 2 * plan.order_a;
   int *order_b = reinterpret_cast<int *>(at), *skeys_b = reinterpret_cast<int *>(at + plan.order_b);
   long long *sums = reinterpret_cast<long long *>(at + 2 * plan.order_b);
-  GF2_RC(enqueue_sort(fn, A, c0, b, base, order_a, skeys_a, s));
-  GF2_RC(enqueue_sort(fn, B, c0, b, base, order_b, skeys_b, s));  // behind A's sort on the stream: the work space is free again
+  GF2_RC(gf2_enqueue_class_sort(fn, A, c0, b, base, order_a, skeys_a, s));
+  GF2_RC(gf2_enqueue_class_sort(fn, B, c0, b, base, order_b, skeys_b, s));  // behind A's sort on the stream: the work space is free again
   GF2_RC(gf2_hip_rc(gf2k_join_count(skeys_a, A->nrows, skeys_b, B->nrows, sums, count, s), fn));
   if (D->nrows == 0) return 0;  // a count-only call
   const hipError_t e = gf2k_join_scatter(A->data, A->ld, A->nrows, B->data, B->ld, B->nrows, A->ncols, order_a, skeys_a, order_b, skeys_b, sums,
@@ -108,23 +81,16 @@ extern "C" int gf2_join_select_dev(gf2_dmat *D, gf2_dmat const *A, gf2_dmat cons
   if (gf2_check_mat(fn, "A", A)) return -1;
   if (gf2_check_mat(fn, "B", B)) return -1;
   if (gf2_check_mat(fn, "D", D, /*unstored_ok=*/true)) return -1;  // D->data null: the rows are not stored
-  if (b < 0 || b > kJoinMaxB) return gf2_bad_arg(fn, "b = " + std::to_string(b) + " is outside 0 <= b <= " + std::to_string(kJoinMaxB));
-  if (B->ncols != A->ncols || D->ncols != A->ncols)
-    return gf2_bad_arg(fn, "A has " + std::to_string(A->ncols) + " columns, B " + std::to_string(B->ncols) + ", D " + std::to_string(D->ncols) +
-                               ": A->ncols, B->ncols and D->ncols must be equal");
-  if (c0 < 0 || (long long)c0 + b > A->ncols)
-    return gf2_bad_arg(fn, "the columns [c0, c0 + b) = [" + std::to_string(c0) + ", " + std::to_string((long long)c0 + b) +
-                               ") are outside A and B (" + std::to_string(A->ncols) + " columns)");
+  GF2_RC(gf2_check_key_bits(fn, b, kJoinMaxB));
+  GF2_RC(gf2_check_equal_ncols(fn, A, B, D));
+  GF2_RC(gf2_check_key_columns(fn, "A and B", A->ncols, c0, b));
   GF2_RC(gf2_check_ptr(fn, "count", count, 8));
   GF2_RC(gf2_check_ptr(fn, "hits", hits, 8));
   GF2_RC(gf2_refuse_misaligned(fn, "ia", ia, 4));
   GF2_RC(gf2_refuse_misaligned(fn, "ib", ib, 4));
   GF2_RC(gf2_refuse_misaligned(fn, "wt", wt, 4));
-  if (wc0 < 0 || wc0 > wc1 || wc1 > A->ncols)
-    return gf2_bad_arg(fn, "the weight range [wc0, wc1) = [" + std::to_string(wc0) + ", " + std::to_string(wc1) + ") is outside 0 <= wc0 <= wc1 <= " +
-                               std::to_string(A->ncols) + " columns");
-  if (wlo < 0 || wlo > whi)
-    return gf2_bad_arg(fn, "the weight window [wlo, whi] = [" + std::to_string(wlo) + ", " + std::to_string(whi) + "] is outside 0 <= wlo <= whi");
+  GF2_RC(gf2_check_weight_range(fn, A->ncols, wc0, wc1));
+  GF2_RC(gf2_check_weight_window(fn, wlo, whi));
   // aliasing, last.  A and B are only read: they may overlap or be one view.  A D without data shares no word with anything
   GF2_RC(gf2_refuse_overlap(fn, "D", D, "A", A));
   GF2_RC(gf2_refuse_overlap(fn, "D", D, "B", B));
@@ -149,8 +115,8 @@ extern "C" int gf2_join_select_dev(gf2_dmat *D, gf2_dmat const *A, gf2_dmat cons
   long long *sums = reinterpret_cast<long long *>(at + 2 * plan.join.order_b);
   long long *hsums = reinterpret_cast<long long *>(base + plan.join.scratch);  // behind everything of the join
   long long *hown = reinterpret_cast<long long *>(base + plan.join.scratch + plan.hit_bytes / 2);
-  GF2_RC(enqueue_sort(fn, A, c0, b, base, order_a, skeys_a, s));
-  GF2_RC(enqueue_sort(fn, B, c0, b, base, order_b, skeys_b, s));  // behind A's sort on the stream: the work space is free again
+  GF2_RC(gf2_enqueue_class_sort(fn, A, c0, b, base, order_a, skeys_a, s));
+  GF2_RC(gf2_enqueue_class_sort(fn, B, c0, b, base, order_b, skeys_b, s));  // behind A's sort on the stream: the work space is free again
   GF2_RC(gf2_hip_rc(gf2k_join_count(skeys_a, A->nrows, skeys_b, B->nrows, sums, count, s), fn));
   GF2_RC(gf2_hip_rc(gf2k_join_weigh(A->data, A->ld, A->nrows, B->data, B->ld, B->nrows, A->ncols, order_a, skeys_a, order_b, skeys_b, hsums,
                                     hown, hits, wc0, wc1, wlo, whi, -1, s),

@@ -1,8 +1,10 @@
-// gf2_lf2.h -- launchers of gf2_lf2.hip (callers: lf2_host.cpp).  Arguments are checked by the callers.  Every launcher only enqueues
-// on `stream`.  key(i) = bits [c0, c0 + b) of row i of P.
+// gf2_lf2.h -- launchers of gf2_lf2.hip and the enqueue of the whole class sort (lf2_host.cpp; callers: lf2_host.cpp, join_host.cpp,
+// draw_host.cpp).  Arguments are checked by the callers.  Everything here only enqueues on `stream`.  key(i) = bits [c0, c0 + b) of row i of P.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "../../../include/m4ri_hip.h"
 
 extern "C" {
 // One pass of the sort, 0 <= pass < lf2_plan(...).passes, over the key bits [8 * pass, ...): stable.  P non-null (the first pass): the
@@ -22,3 +24,8 @@ hipError_t gf2k_lf2_pair_scatter(const uint64_t *P, long long ld, int nrows, int
                                  const long long *offsets, uint64_t *D, long long ldd, int cap, int *lo, int *hi, int lanes,
                                  hipStream_t stream);
 }
+
+// order and (unless null) skeys <- the stable sort of M's rows by their key: the iota for b == 0, else the passes in turn, the first on
+// the matrix, the last into order.  work: lf2_plan(M->nrows, M->ncols, b).sort_scratch bytes (lf2_sort_work cuts them; unused for
+// b == 0), the caller's.  M->nrows > 0; the caller holds gf2_enqueue_mu.  fn: the entry's name, for the message of a failed launch
+int gf2_enqueue_class_sort(const char *fn, gf2_dmat const *M, int c0, int b, void *work, int *order, int *skeys, hipStream_t stream);

@@ -12,7 +12,7 @@
 //     run sums -> offsets, *count                                   gf2_lf2_scan_group_kernel<long long>
 //     D[offset + j] = P[order[s]] ^ P[order[p]]                     gf2_lf2_pair_scatter_kernel<1 | 2 | 8 | 64 lanes per row>
 //
-// The key of a row is read by lf2_key alone: the rule of lf1_key (bkw/gf2_bkw.hip), restated here so that that file stays as it is.
+// The key of a row is read by gf2_row_key (gf2_dev_words.h) alone.
 //
 // WHICH LANE HOLDS WHICH ITEM.  Stability rests on it.  A sort tile is kLf2TileRows consecutive items of the pass's input.  Wave w of
 // the workgroup owns the items [w * kLf2WaveRows, (w + 1) * kLf2WaveRows) of the tile and walks them in rounds of 64: in round j,
@@ -28,43 +28,12 @@
 // Everything is integer arithmetic with one writer per output word: two runs give the same bits.
 #include <hip/hip_runtime.h>
 
+#include "../gf2_dev_words.h"
 #include "../gf2_kernels.h"
 #include "gf2_lf2.h"
 #include "lf2_plan.h"
 
-typedef uint64_t u64;
-typedef uint32_t u32;
-
 namespace {
-
-// where the key lies in a row: word w0 from bit s on, `two`: the window runs on into word w0 + 1 (then s > 0)
-struct Lf2Window {
-  int w0, s, b;
-  bool two;
-  u32 mask;
-};
-
-__device__ __forceinline__ Lf2Window lf2_window(int c0, int b) {
-  Lf2Window w;
-  w.w0 = c0 >> 6;
-  w.s = c0 & 63;
-  w.b = b;
-  w.two = w.s + b > 64;
-  w.mask = (1u << b) - 1;
-  return w;
-}
-
-// bits [c0, c0 + b) of a row: one word, or two funnelled together when the window crosses a word boundary (b <= 30: never three);
-// the second word is read only then, and no word at all for b == 0
-__device__ __forceinline__ u32 lf2_key(const u64 *row, Lf2Window w) {
-  u32 v = 0;
-  if (w.b > 0) {
-    u64 x = row[w.w0] >> w.s;
-    if (w.two) x |= row[w.w0 + 1] << (64 - w.s);
-    v = (u32)x & w.mask;
-  }
-  return v;
-}
 
 // the first position of the class that position s0 of the sorted keys belongs to: steps of 1, 2, 4, ... back while the key is the
 // same (a class of a few rows costs a few loads), then a bisection between the last two
@@ -91,44 +60,7 @@ __device__ __forceinline__ long long lf2_class_start(const int *skeys, long long
   return hi;
 }
 
-// the position of output j of a run: the largest q < n with pre[q] <= j, where pre[q] = the outputs of the positions before q
-// (pre[0] == 0 <= j < the run's total).  Positions without outputs (pre[q] == pre[q + 1]) are never the answer.
-__device__ __forceinline__ int lf2_find_position(const long long *pre, int n, long long j) {
-  int lo = 0, hi = n;  // pre[lo] <= j, and hi == n or pre[hi] > j
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (pre[mid] <= j)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
-// ---- sums over a workgroup
-
-// the sum of `mine` over the lanes before this one, and (in *total) over all.  Every lane calls it; a barrier lies inside, and the
-// caller puts one before wave_sum is used again.
-template <typename T>
-__device__ __forceinline__ T lf2_block_scan(T mine, T *wave_sum, T *total) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  T incl = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T o = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += o;
-  }
-  if (lane == 63) wave_sum[wave] = incl;
-  __syncthreads();
-  T before = incl - mine, all = 0;
-#pragma unroll
-  for (int wv = 0; wv < kLf2Waves; ++wv) {
-    if (wv < wave) before += wave_sum[wv];
-    all += wave_sum[wv];
-  }
-  *total = all;
-  return before;
-}
+// ---- sums over a workgroup (gf2_block_scan)
 
 // parts[k] = the sum of chunk k of v
 __global__ void __launch_bounds__(kLf2Threads) gf2_lf2_scan_sums_kernel(const int *v, long long n, int *parts) {
@@ -138,7 +70,7 @@ __global__ void __launch_bounds__(kLf2Threads) gf2_lf2_scan_sums_kernel(const in
 #pragma unroll
   for (int i = 0; i < kLf2ScanItems; ++i)
     if (k0 + i < n) mine += v[k0 + i];
-  lf2_block_scan<int>(mine, wave_sum, &total);
+  gf2_block_scan<int, kLf2Waves>(mine, wave_sum, &total);
   if (threadIdx.x == 0) parts[blockIdx.x] = total;
 }
 
@@ -155,7 +87,7 @@ __global__ void __launch_bounds__(kLf2Threads) gf2_lf2_scan_group_kernel(T *v, l
       x[i] = k0 + i < n ? v[k0 + i] : 0;
       mine += x[i];
     }
-    T before = running + lf2_block_scan<T>(mine, wave_sum, &all);
+    T before = running + gf2_block_scan<T, kLf2Waves>(mine, wave_sum, &all);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (k0 + i < n) v[k0 + i] = before;
@@ -177,7 +109,7 @@ __global__ void __launch_bounds__(kLf2Threads) gf2_lf2_scan_apply_kernel(int *v,
     x[i] = k0 + i < n ? v[k0 + i] : 0;
     mine += x[i];
   }
-  int before = parts[blockIdx.x] + lf2_block_scan<int>(mine, wave_sum, &total);
+  int before = parts[blockIdx.x] + gf2_block_scan<int, kLf2Waves>(mine, wave_sum, &total);
 #pragma unroll
   for (int i = 0; i < kLf2ScanItems; ++i) {
     if (k0 + i < n) v[k0 + i] = before;
@@ -192,14 +124,14 @@ __global__ void __launch_bounds__(kLf2Threads) gf2_lf2_sort_count_kernel(const u
   __shared__ int cnt[kLf2Digits];
   cnt[threadIdx.x] = 0;
   __syncthreads();
-  const Lf2Window w = lf2_window(c0, b);
+  const Gf2KeyWindow w = gf2_key_window(c0, b);
   const u32 dmask = (1u << bits) - 1;
   const long long base = (long long)blockIdx.x * kLf2TileRows + threadIdx.x;
 #pragma unroll 4
   for (int j = 0; j < kLf2TileItems; ++j) {
     const long long i = base + (long long)j * kLf2Threads;
     if (i < n) {
-      const u32 key = P ? lf2_key(P + i * ld, w) : (u32)in[i].x;
+      const u32 key = P ? gf2_row_key(P + i * ld, w) : (u32)in[i].x;
       atomicAdd(&cnt[(key >> shift) & dmask], 1);
     }
   }
@@ -213,7 +145,7 @@ __global__ void __launch_bounds__(kLf2Threads) gf2_lf2_sort_scatter_kernel(const
                                                                            const int *offsets, int2 *out, int *order, int *skeys) {
   __shared__ int run[kLf2Waves][kLf2Digits];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const Lf2Window w = lf2_window(c0, b);
+  const Gf2KeyWindow w = gf2_key_window(c0, b);
   const u32 dmask = (1u << bits) - 1;
   const long long base = (long long)blockIdx.x * kLf2TileRows + (long long)wave * kLf2WaveRows + lane;
   u32 key[kLf2TileItems];
@@ -225,7 +157,7 @@ __global__ void __launch_bounds__(kLf2Threads) gf2_lf2_sort_scatter_kernel(const
     row[j] = 0;
     if (i < n) {
       if (P) {
-        key[j] = lf2_key(P + i * ld, w);
+        key[j] = gf2_row_key(P + i * ld, w);
         row[j] = (int)i;
       } else {
         const int2 v = in[i];
@@ -340,11 +272,9 @@ __global__ void __launch_bounds__(kLf2Threads) gf2_lf2_pair_count_kernel(const i
   long long mine = 0, total;
 #pragma unroll
   for (int i = 0; i < kLf2RunItems; ++i) mine += r[i];
-  lf2_block_scan<long long>(mine, wave_sum, &total);
+  gf2_block_scan<long long, kLf2Waves>(mine, wave_sum, &total);
   if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
-
-__device__ __forceinline__ u64 lf2_lo_hi(u32 lo, u32 hi) { return (u64)lo | ((u64)hi << 32); }
 
 // d = a ^ p over the nw words of a row, the last one masked; lane `sub` of LANES takes the pairs of words sub, sub + LANES, ...
 // vec_p / vec_d: the rows of P / of D start on 16-byte boundaries, so a pair is one 16-byte access; an odd last word goes alone
@@ -359,8 +289,8 @@ __device__ __forceinline__ void lf2_xor_row(u64 *d, const u64 *a, const u64 *p, 
       if (vec_p) {
         const uint4 x = *reinterpret_cast<const uint4 *>(a + k);
         const uint4 y = *reinterpret_cast<const uint4 *>(p + k);
-        x0 = lf2_lo_hi(x.x ^ y.x, x.y ^ y.y);
-        x1 = lf2_lo_hi(x.z ^ y.z, x.w ^ y.w);
+        x0 = gf2_lo_hi(x.x ^ y.x, x.y ^ y.y);
+        x1 = gf2_lo_hi(x.z ^ y.z, x.w ^ y.w);
       } else {
         x0 = a[k] ^ p[k];
         x1 = a[k + 1] ^ p[k + 1];
@@ -398,7 +328,7 @@ __global__ void __launch_bounds__(kLf2Threads) gf2_lf2_pair_scatter_kernel(const
   long long mine = 0, total;
 #pragma unroll
   for (int i = 0; i < kLf2RunItems; ++i) mine += r[i];
-  long long before = lf2_block_scan<long long>(mine, wave_sum, &total);
+  long long before = gf2_block_scan<long long, kLf2Waves>(mine, wave_sum, &total);
 #pragma unroll
   for (int i = 0; i < kLf2RunItems; ++i) {
     const int q = kLf2RunItems * threadIdx.x + i;
@@ -412,7 +342,7 @@ __global__ void __launch_bounds__(kLf2Threads) gf2_lf2_pair_scatter_kernel(const
   const u64 mlast = ~0ull >> (63 - (int)(((long long)ncols - 1) & 63));
   const int sub = threadIdx.x % LANES;
   for (long long j = threadIdx.x / LANES; j < jmax; j += kLf2Threads / LANES) {
-    const int q = lf2_find_position(pre, kLf2RunRows, j);
+    const int q = gf2_find_position(pre, kLf2RunRows, j);
     const long long p = tpos[q] + (j - pre[q]);
     const int a = order[s0 + q], c = order[p];
     const long long at = off + j;
@@ -422,11 +352,6 @@ __global__ void __launch_bounds__(kLf2Threads) gf2_lf2_pair_scatter_kernel(const
     }
     lf2_xor_row<LANES>(D + at * ldd, P + (long long)a * ld, P + (long long)c * ld, nw, mlast, vec_p, vec_d, sub);
   }
-}
-
-// 16-byte accesses only where every row starts on a 16-byte boundary and a row has a pair of words
-int lf2_rows_aligned16(const u64 *A, long long ld, long long nrows, long long nw) {
-  return nw > 1 && !(reinterpret_cast<uintptr_t>(A) & 15) && (!(ld & 1) || nrows == 1);
 }
 
 }  // namespace
@@ -474,7 +399,7 @@ extern "C" hipError_t gf2k_lf2_pair_scatter(const u64 *P, long long ld, int nrow
   if (plan.passes < 0 || nrows <= 0 || cap <= 0) return hipErrorInvalidValue;
   if (lanes < 0) lanes = plan.lanes;
   const long long nw = ((long long)ncols + 63) >> 6;
-  const int vec_p = lf2_rows_aligned16(P, ld, nrows, nw), vec_d = lf2_rows_aligned16(D, ldd, cap, nw);
+  const int vec_p = gf2_rows_aligned16(P, ld, nrows, nw), vec_d = gf2_rows_aligned16(D, ldd, cap, nw);
   const dim3 grid((unsigned)plan.runs), block(kLf2Threads);
   if (lanes == 1)
     LF2_SCATTER(1);

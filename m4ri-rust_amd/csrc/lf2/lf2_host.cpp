@@ -12,56 +12,28 @@
 #include "gf2_lf2.h"
 #include "lf2_plan.h"
 
-namespace {
-
-int check_window(const char *fn, gf2_dmat const *P, int c0, int b) {
-  if (b < 0 || b > kLf2MaxB) return gf2_bad_arg(fn, "b = " + std::to_string(b) + " is outside 0 <= b <= " + std::to_string(kLf2MaxB));
-  if (c0 < 0 || (long long)c0 + b > P->ncols)
-    return gf2_bad_arg(fn, "the columns [c0, c0 + b) = [" + std::to_string(c0) + ", " + std::to_string((long long)c0 + b) +
-                               ") are outside P (" + std::to_string(P->ncols) + " columns)");
-  return 0;
-}
-
-struct FlatArray {
-  const char *name;
-  const void *p;
-  long long bytes;
-};
-
-int refuse_array_meets_mat(const char *fn, const FlatArray &a, const char *m, gf2_dmat const *M) {
-  if (!a.p || !gf2_range_meets_mat(a.p, a.bytes, M)) return 0;
-  return gf2_bad_arg(fn, std::string(a.name) + " and " + m + " overlap: the address range of " + a.name + " may not meet " + m + "'s");
-}
-
-// every array against the matrices (D may be null) and against the arrays before it
-int refuse_array_overlaps(const char *fn, const FlatArray *arrays, int n, gf2_dmat const *P, gf2_dmat const *D) {
-  for (int i = 0; i < n; ++i) {
-    GF2_RC(refuse_array_meets_mat(fn, arrays[i], "P", P));
-    if (D) GF2_RC(refuse_array_meets_mat(fn, arrays[i], "D", D));
-    for (int j = 0; j < i; ++j)
-      if (arrays[i].p && arrays[j].p && gf2_ranges_meet(arrays[i].p, arrays[i].bytes, arrays[j].p, arrays[j].bytes))
-        return gf2_bad_arg(fn, std::string(arrays[j].name) + " and " + arrays[i].name + " overlap: their address ranges may not meet");
-  }
-  return 0;
-}
-
-// order (and skeys unless null) <- the stable sort of P's rows by their key.  P->nrows > 0; the caller holds gf2_enqueue_mu
-int enqueue_sort(const char *fn, gf2_dmat const *P, int c0, int b, int *order, int *skeys, hipStream_t s) {
-  const Lf2Plan plan = lf2_plan(P->nrows, P->ncols, b);
-  if (plan.passes == 0) return gf2_hip_rc(gf2k_lf2_iota(P->nrows, order, skeys, s), fn);
-  void *scratch = nullptr;
-  GF2_RC(gf2_stream_scratch(s, (size_t)plan.sort_scratch, &scratch, GF2_SLOT_LF2_SORT));
-  char *base = static_cast<char *>(scratch);
-  void *pairs[2] = {base, base + plan.pair_bytes};
-  int *counts = reinterpret_cast<int *>(base + 2 * plan.pair_bytes);
-  int *parts = reinterpret_cast<int *>(base + 2 * plan.pair_bytes + plan.count_bytes);
+int gf2_enqueue_class_sort(const char *fn, gf2_dmat const *M, int c0, int b, void *work, int *order, int *skeys, hipStream_t s) {
+  const Lf2Plan plan = lf2_plan(M->nrows, M->ncols, b);
+  if (plan.passes == 0) return gf2_hip_rc(gf2k_lf2_iota(M->nrows, order, skeys, s), fn);
+  const Lf2SortWork w = lf2_sort_work(work, plan);
   for (int pass = 0; pass < plan.passes; ++pass) {
     const bool first = pass == 0, last = pass == plan.passes - 1;
-    const hipError_t e = gf2k_lf2_sort_pass(first ? P->data : nullptr, P->ld, c0, b, first ? nullptr : pairs[(pass - 1) & 1], P->nrows, pass,
-                                            counts, parts, last ? nullptr : pairs[pass & 1], last ? order : nullptr, last ? skeys : nullptr, s);
+    const hipError_t e = gf2k_lf2_sort_pass(first ? M->data : nullptr, M->ld, c0, b, first ? nullptr : w.pairs[(pass - 1) & 1], M->nrows, pass,
+                                            w.counts, w.parts, last ? nullptr : w.pairs[pass & 1], last ? order : nullptr,
+                                            last ? skeys : nullptr, s);
     GF2_RC(gf2_hip_rc(e, fn));
   }
   return 0;
+}
+
+namespace {
+
+// the sort in a work space of its own from the stream's arena (none for b == 0: the iota needs none).  The caller holds gf2_enqueue_mu
+int sort_in_arena(const char *fn, gf2_dmat const *P, int c0, int b, int *order, int *skeys, hipStream_t s) {
+  void *work = nullptr;
+  const Lf2Plan plan = lf2_plan(P->nrows, P->ncols, b);
+  if (plan.passes > 0) GF2_RC(gf2_stream_scratch(s, (size_t)plan.sort_scratch, &work, GF2_SLOT_LF2_SORT));
+  return gf2_enqueue_class_sort(fn, P, c0, b, work, order, skeys, s);
 }
 
 }  // namespace
@@ -69,16 +41,17 @@ int enqueue_sort(const char *fn, gf2_dmat const *P, int c0, int b, int *order, i
 extern "C" int gf2_class_sort_dev(gf2_dmat const *P, int c0, int b, int *order, int *skeys, void *stream) {
   static const char fn[] = "gf2_class_sort_dev";
   if (gf2_check_mat(fn, "P", P)) return -1;
-  GF2_RC(check_window(fn, P, c0, b));
+  GF2_RC(gf2_check_key_window(fn, "P", P->ncols, c0, b, kLf2MaxB));
   GF2_RC(gf2_check_ptr(fn, "order", order, 4));
   GF2_RC(gf2_refuse_misaligned(fn, "skeys", skeys, 4));
   // aliasing, last
-  const FlatArray arrays[2] = {{"order", order, 4ll * P->nrows}, {"skeys", skeys, 4ll * P->nrows}};
-  GF2_RC(refuse_array_overlaps(fn, arrays, 2, P, nullptr));
+  const Gf2FlatArray arrays[2] = {{"order", order, 4ll * P->nrows}, {"skeys", skeys, 4ll * P->nrows}};
+  const Gf2NamedMat mat = {"P", P};
+  GF2_RC(gf2_refuse_array_overlaps(fn, arrays, 2, &mat, 1));
   GF2_RC(gf2_require_device_for(fn));
   if (P->nrows == 0) return 0;
   std::lock_guard<std::mutex> lk(gf2_enqueue_mu);  // another thread on the same stream would be handed the same scratch
-  return enqueue_sort(fn, P, c0, b, order, skeys, static_cast<hipStream_t>(stream));
+  return sort_in_arena(fn, P, c0, b, order, skeys, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int gf2_lf2_reduce_dev(gf2_dmat *D, gf2_dmat const *P, int c0, int b, long long *count, int *lo, int *hi, void *stream) {
@@ -86,7 +59,7 @@ extern "C" int gf2_lf2_reduce_dev(gf2_dmat *D, gf2_dmat const *P, int c0, int b,
   if (gf2_check_mat(fn, "P", P)) return -1;
   if (gf2_check_mat(fn, "D", D)) return -1;
   if (D->nrows > 0) GF2_RC(gf2_refuse_null(fn, "D.data", D->data));  // also where a row has no word
-  GF2_RC(check_window(fn, P, c0, b));
+  GF2_RC(gf2_check_key_window(fn, "P", P->ncols, c0, b, kLf2MaxB));
   if (D->ncols != P->ncols)
     return gf2_bad_arg(fn, "D has " + std::to_string(D->ncols) + " columns, P " + std::to_string(P->ncols) + ": D->ncols must equal P->ncols");
   GF2_RC(gf2_check_ptr(fn, "count", count, 8));
@@ -94,8 +67,9 @@ extern "C" int gf2_lf2_reduce_dev(gf2_dmat *D, gf2_dmat const *P, int c0, int b,
   GF2_RC(gf2_refuse_misaligned(fn, "hi", hi, 4));
   // aliasing, last
   GF2_RC(gf2_refuse_overlap(fn, "D", D, "P", P));
-  const FlatArray arrays[3] = {{"count", count, 8}, {"lo", lo, 4ll * D->nrows}, {"hi", hi, 4ll * D->nrows}};
-  GF2_RC(refuse_array_overlaps(fn, arrays, 3, P, D));
+  const Gf2FlatArray arrays[3] = {{"count", count, 8}, {"lo", lo, 4ll * D->nrows}, {"hi", hi, 4ll * D->nrows}};
+  const Gf2NamedMat mats[2] = {{"P", P}, {"D", D}};
+  GF2_RC(gf2_refuse_array_overlaps(fn, arrays, 3, mats, 2));
   GF2_RC(gf2_require_device_for(fn));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (P->nrows == 0) return gf2_hip_rc(hipMemsetAsync(count, 0, 8, s), fn);
@@ -106,7 +80,7 @@ extern "C" int gf2_lf2_reduce_dev(gf2_dmat *D, gf2_dmat const *P, int c0, int b,
   char *base = static_cast<char *>(scratch);
   int *order = reinterpret_cast<int *>(base), *skeys = reinterpret_cast<int *>(base + plan.order_bytes);
   long long *sums = reinterpret_cast<long long *>(base + 2 * plan.order_bytes);
-  GF2_RC(enqueue_sort(fn, P, c0, b, order, skeys, s));
+  GF2_RC(sort_in_arena(fn, P, c0, b, order, skeys, s));
   GF2_RC(gf2_hip_rc(gf2k_lf2_pair_count(skeys, P->nrows, sums, count, s), fn));
   if (D->nrows == 0) return 0;  // a count-only call
   const hipError_t e = gf2k_lf2_pair_scatter(P->data, P->ld, P->nrows, P->ncols, order, skeys, sums, D->data, D->ld, D->nrows, lo, hi, -1, s);

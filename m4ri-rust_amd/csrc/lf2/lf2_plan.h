@@ -61,6 +61,16 @@ inline Lf2Plan lf2_plan(long long nrows, long long ncols, int b) {
   return p;
 }
 
+// the sort's work space, sort_scratch bytes from `base` on: two pair buffers, the digit counts, the chunk sums of their scan
+struct Lf2SortWork {
+  void *pairs[2];
+  int *counts, *parts;
+};
+inline Lf2SortWork lf2_sort_work(void *base, const Lf2Plan &p) {
+  char *at = static_cast<char *>(base);
+  return {{at, at + p.pair_bytes}, reinterpret_cast<int *>(at + 2 * p.pair_bytes), reinterpret_cast<int *>(at + 2 * p.pair_bytes + p.count_bytes)};
+}
+
 // the bits of pass `pass`: [kLf2DigitBits * pass, ...) of the key
 inline int lf2_pass_bits(int b, int pass) {
   const int left = b - kLf2DigitBits * pass;

@@ -19,12 +19,10 @@
 #include <hip/hip_runtime.h>
 
 #include "../../../include/m4ri_hip_near.h"
+#include "../gf2_dev_words.h"
 #include "../gf2_kernels.h"
 #include "gf2_near.h"
 #include "near_plan.h"
-
-typedef uint64_t u64;
-typedef uint32_t u32;
 
 namespace {
 
@@ -50,16 +48,6 @@ struct NearArgs {
 };
 
 // ---- word-level helpers: plain values and pointers, no thread index (tests/test_near_helpers_cpu.py runs their text on the CPU)
-
-// the bits of word k of a row that are columns of [wc0, wc1); a word outside the range has none
-__device__ __forceinline__ u64 near_word_mask(long long k, int wc0, int wc1) {
-  const long long lo = 64 * k, hi = lo + 64;
-  if (wc0 >= wc1 || wc1 <= lo || wc0 >= hi) return 0;
-  u64 m = ~0ull;
-  if (wc0 > lo) m &= ~0ull << (wc0 - lo);
-  if (wc1 < hi) m &= ~0ull >> (hi - wc1);
-  return m;
-}
 
 // is a pair of weight w a hit of the window [wlo, wlo + span]?  One unsigned comparison: a w below wlo wraps to a large number
 __device__ __forceinline__ int near_in_window(int w, int wlo, u32 span) { return (u32)(w - wlo) <= span; }
@@ -100,7 +88,7 @@ __device__ __forceinline__ int near_weight(const u64 (&a)[W], const u64 (&b)[W])
 // the ones of x ^ y in the columns [wc0, wc1), read from the rows themselves: only the words [first, end) of the range are read
 __device__ __forceinline__ int near_row_weight(const u64 *x, const u64 *y, long long first, long long end, int wc0, int wc1) {
   int w = 0;
-  for (long long k = first; k < end; ++k) w += __popcll((x[k] ^ y[k]) & near_word_mask(k, wc0, wc1));
+  for (long long k = first; k < end; ++k) w += __popcll((x[k] ^ y[k]) & gf2_word_mask(k, wc0, wc1));
   return w;
 }
 
@@ -218,7 +206,7 @@ __global__ void __launch_bounds__(kNearThreads) gf2_near_kernel(NearArgs p) {
     s[r].best = kNearNoKey;
 #pragma unroll
     for (int k = 0; k < W; ++k)
-      a[r][k] = s[r].i < p.na && k < words ? p.A[s[r].i * p.lda + first + k] & near_word_mask(first + k, p.wc0, p.wc1) : 0;
+      a[r][k] = s[r].i < p.na && k < words ? p.A[s[r].i * p.lda + first + k] & gf2_word_mask(first + k, p.wc0, p.wc1) : 0;
     if (MODE == kNearSelect) {
       near_cell_window(p, c, s[r]);
       writes |= s[r].lim > 0;
@@ -232,7 +220,7 @@ __global__ void __launch_bounds__(kNearThreads) gf2_near_kernel(NearArgs p) {
     __syncthreads();  // the tile before this one has been read by every lane
     for (int e = threadIdx.x; e < n * W; e += kNearThreads) {
       const int k = e % W;
-      tile[e] = k < words ? p.B[(t0 + e / W) * p.ldb + first + k] & near_word_mask(first + k, p.wc0, p.wc1) : 0;
+      tile[e] = k < words ? p.B[(t0 + e / W) * p.ldb + first + k] & gf2_word_mask(first + k, p.wc0, p.wc1) : 0;
     }
     __syncthreads();
     if (cls == 0)
@@ -290,6 +278,7 @@ __global__ void __launch_bounds__(kNearThreads) gf2_near_scan_kernel(long long *
       x[i] = k0 + i < n ? v[k0 + i] : 0;
       mine += x[i];
     }
+    // the wave scan written out, not gf2_block_scan: with the call this kernel compiles to other code (40 -> 48 VGPRs)
     long long incl = mine;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {

@@ -20,12 +20,6 @@ int check_pools(const char *fn, gf2_dmat const *A, gf2_dmat const *B) {
   if (gf2_check_mat(fn, "B", B)) return -1;
   return 0;
 }
-int check_range(const char *fn, gf2_dmat const *A, int wc0, int wc1) {
-  if (wc0 < 0 || wc0 > wc1 || wc1 > A->ncols)
-    return gf2_bad_arg(fn, "the weight range [wc0, wc1) = [" + std::to_string(wc0) + ", " + std::to_string(wc1) + ") is outside 0 <= wc0 <= wc1 <= " +
-                               std::to_string(A->ncols) + " columns");
-  return 0;
-}
 int check_flags(const char *fn, int flags) {
   if (flags & ~(GF2_NEAR_OFF_DIAGONAL | GF2_NEAR_UPPER))
     return gf2_bad_arg(fn, "flags = " + std::to_string(flags) + " has bits other than GF2_NEAR_OFF_DIAGONAL (1) and GF2_NEAR_UPPER (2)");
@@ -42,16 +36,13 @@ extern "C" int gf2_near_pairs_dev(gf2_dmat *D, gf2_dmat const *A, gf2_dmat const
   static const char fn[] = "gf2_near_pairs_dev";
   GF2_RC(check_pools(fn, A, B));
   if (gf2_check_mat(fn, "D", D, /*unstored_ok=*/true)) return -1;  // D->data null: the rows are not stored
-  if (B->ncols != A->ncols || D->ncols != A->ncols)
-    return gf2_bad_arg(fn, "A has " + std::to_string(A->ncols) + " columns, B " + std::to_string(B->ncols) + ", D " + std::to_string(D->ncols) +
-                               ": A->ncols, B->ncols and D->ncols must be equal");
+  GF2_RC(gf2_check_equal_ncols(fn, A, B, D));
   GF2_RC(gf2_check_ptr(fn, "hits", hits, 8));
   GF2_RC(gf2_refuse_misaligned(fn, "ia", ia, 4));
   GF2_RC(gf2_refuse_misaligned(fn, "ib", ib, 4));
   GF2_RC(gf2_refuse_misaligned(fn, "wt", wt, 4));
-  GF2_RC(check_range(fn, A, wc0, wc1));
-  if (wlo < 0 || wlo > whi)
-    return gf2_bad_arg(fn, "the weight window [wlo, whi] = [" + std::to_string(wlo) + ", " + std::to_string(whi) + "] is outside 0 <= wlo <= whi");
+  GF2_RC(gf2_check_weight_range(fn, A->ncols, wc0, wc1));
+  GF2_RC(gf2_check_weight_window(fn, wlo, whi));
   GF2_RC(check_flags(fn, flags));
   // aliasing, last.  A and B are only read: they may overlap or be one view.  A D without data shares no word with anything
   GF2_RC(gf2_refuse_overlap(fn, "D", D, "A", A));
@@ -82,7 +73,7 @@ extern "C" int gf2_nearest_dev(gf2_dmat const *A, gf2_dmat const *B, int wc0, in
   if (!idx && !dist) return gf2_bad_arg(fn, "idx and dist are both null: one of them must be given");
   GF2_RC(gf2_refuse_misaligned(fn, "idx", idx, 4));
   GF2_RC(gf2_refuse_misaligned(fn, "dist", dist, 4));
-  GF2_RC(check_range(fn, A, wc0, wc1));
+  GF2_RC(gf2_check_weight_range(fn, A->ncols, wc0, wc1));
   GF2_RC(check_flags(fn, flags));
   // aliasing, last
   const Gf2FlatArray arrays[2] = {{"idx", idx, 4ll * A->nrows}, {"dist", dist, 4ll * A->nrows}};

@@ -17,31 +17,14 @@
 // Everything is integer arithmetic with one writer per output word and no atomics: two runs give the same bits.
 #include <hip/hip_runtime.h>
 
+#include "../gf2_dev_words.h"
 #include "../gf2_kernels.h"
 #include "gf2_sums.h"
 #include "sums_plan.h"
 
-typedef uint64_t u64;
-typedef uint32_t u32;
-
 namespace {
 
-// ---- word-level helpers: plain values, no thread index (tests/test_sums_helpers_cpu.py runs their text on the CPU)
-
-// the ones of word k of a row, value x, that lie in the columns [wc0, wc1): the first and the last word of the range are masked, a
-// word outside it counts nothing
-__device__ __forceinline__ int sums_word_weight(u64 x, long long k, int wc0, int wc1) {
-  const long long lo = 64 * k, hi = lo + 64;
-  if (wc0 >= wc1 || wc1 <= lo || wc0 >= hi) return 0;
-  u64 m = ~0ull;
-  if (wc0 > lo) m &= ~0ull << (wc0 - lo);
-  if (wc1 < hi) m &= ~0ull >> (hi - wc1);
-  return __popcll(x & m);
-}
-
 // ---- rows
-
-__device__ __forceinline__ u64 sums_lo_hi(u32 lo, u32 hi) { return (u64)lo | ((u64)hi << 32); }
 
 // two words of a row from word k on
 struct SumsPair {
@@ -54,8 +37,8 @@ __device__ __forceinline__ SumsPair sums_load2(const u64 *row, long long k, long
   SumsPair x;
   if (vec && k + 1 < nw) {
     const uint4 v = *reinterpret_cast<const uint4 *>(row + k);
-    x.a = sums_lo_hi(v.x, v.y);
-    x.b = sums_lo_hi(v.z, v.w);
+    x.a = gf2_lo_hi(v.x, v.y);
+    x.b = gf2_lo_hi(v.z, v.w);
   } else {
     x.a = row[k];
     x.b = 0;
@@ -101,11 +84,11 @@ __device__ __forceinline__ int sums_emit(u64 *d, long long k, long long nw, u64 
         d[k + 1] = x.b;
       }
     }
-    return sums_word_weight(x.a, k, wc0, wc1) + sums_word_weight(x.b, k + 1, wc0, wc1);
+    return gf2_word_weight(x.a, k, wc0, wc1) + gf2_word_weight(x.b, k + 1, wc0, wc1);
   }
   x.a &= mlast;
   if (d) d[k] = x.a;
-  return sums_word_weight(x.a, k, wc0, wc1);
+  return gf2_word_weight(x.a, k, wc0, wc1);
 }
 
 template <int LANES, bool STAGED>
@@ -195,11 +178,6 @@ __global__ void __launch_bounds__(kSumsThreads) gf2_unrank_subsets_kernel(const 
     if (i < p) idx[t * p + i] = (int)c[i];
 }
 
-// 16-byte accesses only where every row starts on a 16-byte boundary and a row has a pair of words
-int sums_rows_aligned16(const u64 *M, long long ld, long long nrows, long long nw) {
-  return M && nw > 1 && !(reinterpret_cast<uintptr_t>(M) & 15) && (!(ld & 1) || nrows == 1);
-}
-
 }  // namespace
 
 #define SUMS_LAUNCH(LANES, STAGED)                                                                                                        \
@@ -212,8 +190,8 @@ extern "C" hipError_t gf2k_subset_sums(const u64 *S, long long lds_, int n, cons
   const SumsPlan plan = sums_plan(n, ncols, p, count);
   if (plan.id < 0 || count <= 0 || n < p || (!D && !idx && !wt)) return hipErrorInvalidValue;
   const long long nw = ((long long)ncols + 63) >> 6;
-  const int vec_s = sums_rows_aligned16(S, lds_, n, nw), vec_b = sums_rows_aligned16(base, nw, 1, nw),
-            vec_d = sums_rows_aligned16(D, ldd, count, nw);
+  const int vec_s = gf2_rows_aligned16(S, lds_, n, nw), vec_b = base ? gf2_rows_aligned16(base, nw, 1, nw) : 0,
+            vec_d = D ? gf2_rows_aligned16(D, ldd, count, nw) : 0;
   const dim3 grid((unsigned)plan.groups), block(kSumsThreads);
   const int id = global_s ? (plan.id | 4) : plan.id;
   switch (id) {

@@ -47,9 +47,7 @@ extern "C" int gf2_subset_sums_dev(gf2_dmat *D, gf2_dmat const *S, gf2_dmat cons
                                std::to_string(D->nrows) + ") are outside [0, C(n, p)) = [0, " + std::to_string(total) + ")");
   GF2_RC(gf2_refuse_misaligned(fn, "idx", idx, 4));
   GF2_RC(gf2_refuse_misaligned(fn, "wt", wt, 4));
-  if (wc0 < 0 || wc0 > wc1 || wc1 > S->ncols)
-    return gf2_bad_arg(fn, "the weight range [wc0, wc1) = [" + std::to_string(wc0) + ", " + std::to_string(wc1) + ") is outside 0 <= wc0 <= wc1 <= " +
-                               std::to_string(S->ncols) + " columns");
+  GF2_RC(gf2_check_weight_range(fn, S->ncols, wc0, wc1));
   const bool stored = D->data != nullptr && D->ncols > 0;
   if (D->nrows > 0 && !D->data && !idx && !wt)
     return gf2_bad_arg(fn, "D.data is null and so are idx and wt: rows that are not stored need idx or wt");

@@ -24,16 +24,12 @@
 // global memory, so the result does not depend on how workgroups interleave.
 #include <hip/hip_runtime.h>
 
+#include "../gf2_dev_words.h"
 #include "../gf2_kernels.h"
 #include "gf2_weight.h"
 #include "weight_plan.h"
 
-typedef uint64_t u64;
-typedef uint32_t u32;
-
 namespace {
-
-__device__ __forceinline__ u64 weight_lo_hi(u32 lo, u32 hi) { return (u64)lo | ((u64)hi << 32); }
 
 // the set bits of the words sub, sub + LANES, ... of a row (pairs of words where vec); mlast masks word nw - 1
 template <int LANES>
@@ -46,9 +42,9 @@ __device__ __forceinline__ int weight_row_partial(const u64 *a, long long nw, u6
       const long long k = 2 * u;
       if (k + 1 < nw) {
         const uint4 x = *reinterpret_cast<const uint4 *>(a + k);
-        u64 v1 = weight_lo_hi(x.z, x.w);
+        u64 v1 = gf2_lo_hi(x.z, x.w);
         if (k + 1 == nw - 1) v1 &= mlast;
-        c += __popcll(weight_lo_hi(x.x, x.y)) + __popcll(v1);
+        c += __popcll(gf2_lo_hi(x.x, x.y)) + __popcll(v1);
       } else {
         c += __popcll(a[k] & mlast);
       }
@@ -125,11 +121,11 @@ __global__ void __launch_bounds__(kWeightThreads) gf2_weight_total_kernel(const 
 // a full adder on three words, l = their sum bit and h = their carry bit: one v_bitop3_b32 per half word each (truth tables with
 // a = 0xF0, b = 0xCC, c = 0xAA: a ^ b ^ c = 0x96, majority = 0xE8)
 __device__ __forceinline__ u64 weight_sum3(u64 a, u64 b, u64 c) {
-  return weight_lo_hi(__builtin_amdgcn_bitop3_b32((u32)a, (u32)b, (u32)c, 0x96),
+  return gf2_lo_hi(__builtin_amdgcn_bitop3_b32((u32)a, (u32)b, (u32)c, 0x96),
                       __builtin_amdgcn_bitop3_b32((u32)(a >> 32), (u32)(b >> 32), (u32)(c >> 32), 0x96));
 }
 __device__ __forceinline__ u64 weight_carry3(u64 a, u64 b, u64 c) {
-  return weight_lo_hi(__builtin_amdgcn_bitop3_b32((u32)a, (u32)b, (u32)c, 0xE8),
+  return gf2_lo_hi(__builtin_amdgcn_bitop3_b32((u32)a, (u32)b, (u32)c, 0xE8),
                       __builtin_amdgcn_bitop3_b32((u32)(a >> 32), (u32)(b >> 32), (u32)(c >> 32), 0xE8));
 }
 #define WEIGHT_CSA(h, l, a, b, c)                  \
@@ -200,8 +196,8 @@ __device__ __forceinline__ void weight_load_block(const u64 *a, long long ld, lo
     u64 w0, w1;
     if (WIDE) {
       const uint4 v = *reinterpret_cast<const uint4 *>(p);
-      w0 = weight_lo_hi(v.x, v.y);
-      w1 = weight_lo_hi(v.z, v.w);
+      w0 = gf2_lo_hi(v.x, v.y);
+      w1 = gf2_lo_hi(v.z, v.w);
     } else {
       w0 = p[0];
       w1 = p[second];
@@ -357,17 +353,12 @@ __global__ void __launch_bounds__(kWeightThreads) gf2_weight_select_scatter_kern
     }
 }
 
-// 16-byte loads only where every row starts on a 16-byte boundary and a row has a pair of words
-bool weight_rows_aligned16(const u64 *A, long long ld, long long nrows, long long nw) {
-  return nw > 1 && !(reinterpret_cast<uintptr_t>(A) & 15) && (!(ld & 1) || nrows == 1);
-}
-
 }  // namespace
 
 extern "C" hipError_t gf2k_weight_rows_narrow(const u64 *A, long long ld, int nrows, int ncols, int *weights, hipStream_t stream) {
   if (nrows <= 0 || ncols <= 0) return hipSuccess;
   const long long nw = ((long long)ncols + 63) >> 6;
-  const int vec = nw > 1 && !(reinterpret_cast<uintptr_t>(A) & 15) && (!(ld & 1) || nrows == 1);
+  const int vec = gf2_rows_aligned16(A, ld, nrows, nw);
   const long long blocks = ((long long)nrows + 255) / 256;
   hipLaunchKernelGGL(gf2_weight_rows_narrow_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, stream, A, ld,
                      (long long)nrows, ncols, vec, weights);
@@ -378,7 +369,7 @@ extern "C" hipError_t gf2k_weight_rows(const u64 *A, long long ld, int nrows, in
   if (nrows <= 0 || ncols <= 0) return hipSuccess;
   const WeightRowsPlan plan = weight_rows_plan(nrows, ncols);
   if (plan.variant == 0) return gf2k_weight_rows_narrow(A, ld, nrows, ncols, weights, stream);
-  const int vec = weight_rows_aligned16(A, ld, nrows, ((long long)ncols + 63) >> 6);
+  const int vec = gf2_rows_aligned16(A, ld, nrows, ((long long)ncols + 63) >> 6);
   const long long blocks = ((long long)nrows + plan.rows - 1) / plan.rows;
   const dim3 grid((unsigned)(blocks > (1 << 20) ? (1 << 20) : blocks));
   if (plan.lanes == 8)
@@ -392,7 +383,7 @@ extern "C" hipError_t gf2k_weight_rows(const u64 *A, long long ld, int nrows, in
 extern "C" hipError_t gf2k_weight_total(const u64 *A, long long ld, int nrows, int ncols, unsigned long long *total, hipStream_t stream) {
   if (nrows <= 0 || ncols <= 0) return hipSuccess;
   const WeightTotalPlan plan = weight_total_plan(nrows, ncols);
-  const int vec = weight_rows_aligned16(A, ld, nrows, ((long long)ncols + 63) >> 6);
+  const int vec = gf2_rows_aligned16(A, ld, nrows, ((long long)ncols + 63) >> 6);
   const long long blocks = ((long long)nrows + plan.rows - 1) / plan.rows;
   const dim3 grid((unsigned)(blocks > kWeightTotalBlocks ? kWeightTotalBlocks : blocks));
   if (plan.lanes == 1)
@@ -409,7 +400,7 @@ extern "C" hipError_t gf2k_weight_cols(const u64 *A, long long ld, int nrows, in
   if (nrows <= 0 || ncols <= 0) return hipSuccess;
   const WeightColsPlan plan = weight_cols_plan(nrows, ncols);
   if (plan.bands > 1 && !partial) return hipErrorInvalidValue;
-  const bool vec = weight_rows_aligned16(A, ld, nrows, ((long long)ncols + 63) >> 6);
+  const bool vec = gf2_rows_aligned16(A, ld, nrows, ((long long)ncols + 63) >> 6);
   const dim3 grid((unsigned)plan.groups, (unsigned)plan.bands);  // groups < 2^19, bands <= 1024
   const size_t lds = sizeof(int) * 128 * (size_t)plan.wx;
   int *out = plan.bands > 1 ? partial : weights;

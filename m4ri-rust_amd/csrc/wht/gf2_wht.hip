@@ -35,6 +35,7 @@ namespace {
 
 // Rows by a grid-stride loop, a lane per row.  The index is bits [c0, c0 + k) of the row: one word, or two funnelled together when
 // the range crosses a word boundary (k <= 30: never three); the second word is read only then, and no word at all for k == 0.
+// The rule of gf2_row_key (gf2_dev_words.h) written out, not a call of it: with the call the LDS kernel compiles to other code.
 template <bool LDS>
 __global__ void __launch_bounds__(kWhtTallyThreads) gf2_wht_tally_kernel(const u64 *P, long long ld, long long nrows, int c0, int k,
                                                                          int label_col, u32 *f) {

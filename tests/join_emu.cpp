@@ -1,11 +1,9 @@
-// join_emu.cpp -- the word-level helpers of the join kernels (join_lower_bound, join_upper_bound, join_find_position and
-// join_word_weight of m4ri-rust_amd/csrc/join/gf2_join.hip, cut out of the shipped file by tests/test_join_helpers_cpu.py) on the CPU
-// under the host compiler's address and undefined-behaviour sanitizers.
+// join_emu.cpp -- the word-level helpers that the join kernels keep for themselves (join_lower_bound and join_upper_bound of
+// m4ri-rust_amd/csrc/join/gf2_join.hip, cut out of the shipped file by tests/test_join_helpers_cpu.py) on the CPU under the host
+// compiler's address and undefined-behaviour sanitizers.  The position of an output and the weight of a column range are shared
+// helpers: dev_words_emu.cpp.
 //   the bounds: sorted keys in a heap block of exactly hi ints, handed over shifted so that only [lo, hi) may be read, against a
 //   linear walk: the first and the last element, keys that are absent, below all and above all, one giant class.
-//   the position of an output: sums with empty positions, with one giant position and with 64-bit totals, against a linear search.
-//   the weight of a column range: every [wc0, wc1) of a row of ncols bits, summed over the words that hold a bit of the range (each in
-//   a heap block of its own), against a bit-by-bit count; words outside the range must count nothing.
 #include "kernel_emu.h"
 
 namespace {
@@ -75,96 +73,9 @@ static long check_bounds() {
   return cases;
 }
 
-static long check_positions() {
-  std::mt19937_64 rng(11);
-  long cases = 0;
-  for (int kind = 0; kind < 5; ++kind)
-    for (int n : {1, 2, 3, 64, 1000, 1024}) {
-      std::vector<long long> r(n), pre(n);
-      for (int q = 0; q < n; ++q) {
-        switch (kind) {
-          case 0: r[q] = (long long)(rng() % 4); break;                          // many empty positions
-          case 1: r[q] = q == n / 2 ? 3000000000ll : 0; break;                   // one giant position, the rest empty
-          case 2: r[q] = (long long)q + 2000000000ll; break;                     // a giant class of B: 64-bit totals
-          case 3: r[q] = q == n - 1 ? 5 : 0; break;                              // only the last position
-          default: r[q] = q == 0 ? 7 : (long long)(rng() % 2); break;
-        }
-      }
-      long long total = 0;
-      for (int q = 0; q < n; ++q) {
-        pre[q] = total;
-        total += r[q];
-      }
-      if (total == 0) continue;
-      long long *p = new long long[n];  // a heap block of exactly n sums
-      std::copy(pre.begin(), pre.end(), p);
-      std::vector<long long> js = {0, total - 1, total / 2, total / 3};
-      for (int q = 0; q < n; ++q)
-        if (r[q]) {
-          js.push_back(pre[q]);
-          js.push_back(pre[q] + r[q] - 1);
-        }
-      for (long long j : js) {
-        int want = 0;
-        while (!(pre[want] <= j && j < pre[want] + r[want])) ++want;
-        const int got = join_find_position(p, n, j);
-        if (got != want) {
-          printf("kind %d n %d output %lld: position %d, by search %d\n", kind, n, j, got, want);
-          return -1;
-        }
-        ++cases;
-      }
-      delete[] p;
-    }
-  return cases;
-}
-
-static long check_weights() {
-  const int widths[] = {1, 63, 64, 65, 130};
-  std::mt19937_64 rng(2026);
-  long cases = 0;
-  for (int ncols : widths) {
-    const int nw = (ncols + 63) >> 6;
-    for (int rep = 0; rep < 3; ++rep) {
-      std::vector<u64> row(nw);
-      for (int k = 0; k < nw; ++k) row[k] = rep == 0 ? rng() : rep == 1 ? ~0ull : (0xAAAAAAAAAAAAAAAAull >> (k & 1));
-      for (int wc0 = 0; wc0 <= ncols; ++wc0)
-        for (int wc1 = wc0; wc1 <= ncols; ++wc1) {
-          int want = 0;
-          for (int c = wc0; c < wc1; ++c) want += (int)((row[c >> 6] >> (c & 63)) & 1);
-          int got = 0;
-          for (int k = 0; k < nw; ++k) {
-            const bool holds = wc0 < wc1 && 64 * k < wc1 && wc0 < 64 * (k + 1);
-            u64 *word = new u64[1];  // a word of the range in a block of its own
-            word[0] = row[k];
-            const int w = join_word_weight(word[0], k, wc0, wc1);
-            delete[] word;
-            if (!holds && w != 0) {
-              printf("ncols %d [%d, %d): word %d is outside the range and counts %d\n", ncols, wc0, wc1, k, w);
-              return -1;
-            }
-            got += w;
-          }
-          if (got != want) {
-            printf("ncols %d [%d, %d): weight %d, by bits %d\n", ncols, wc0, wc1, got, want);
-            return -1;
-          }
-          ++cases;
-        }
-    }
-  }
-  return cases;
-}
-
 int main() {
   const long bounds = check_bounds();
   if (bounds < 0) return 1;
   printf("%ld bounds ok\n", bounds);
-  const long positions = check_positions();
-  if (positions < 0) return 1;
-  printf("%ld positions ok\n", positions);
-  const long weights = check_weights();
-  if (weights < 0) return 1;
-  printf("%ld weights ok\n", weights);
   return 0;
 }

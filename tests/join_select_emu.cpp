@@ -1,9 +1,9 @@
 // join_select_emu.cpp -- the word-level helpers of the weight-filtered join (join_select_first_word, join_select_end_word,
-// join_select_is_hit and join_select_pair_weight of m4ri-rust_amd/csrc/join/gf2_join_select.inc, with join_word_weight, join_lo_hi and
-// join_load2 of gf2_join.hip that they call; cut out of the shipped files by tests/test_join_select_helpers_cpu.py) on the CPU under
+// join_select_is_hit and join_select_pair_weight of m4ri-rust_amd/csrc/join/gf2_join_select.inc, with gf2_word_weight, gf2_lo_hi and
+// gf2_load2 of gf2_dev_words.h that they call; cut out of the shipped files by tests/test_join_select_helpers_cpu.py) on the CPU under
 // the host compiler's address and undefined-behaviour sanitizers.
 //   the words of a range: for every [wc0, wc1) of a row of ncols bits, [first, end) are exactly the words that hold a column of the
-//   range, and the weights of those words alone (join_word_weight) sum to the bit-by-bit count.
+//   range, and the weights of those words alone (gf2_word_weight) sum to the bit-by-bit count.
 //   the weight of a pair: rows a and p in heap blocks of exactly the row's words (16-byte aligned, so that the 16-byte form may run
 //   too), dealt to 1, 2, 8 and 64 lanes, with and without 16-byte accesses: the lanes' sums equal the bit-by-bit count of a ^ p on the
 //   range, excess bits of the last word set or not.  A read of a word behind the row is an error of the address sanitizer.
@@ -51,7 +51,7 @@ int main() {
                      first, end);
               return 1;
             }
-            if (holds) got += join_word_weight(a[k] ^ p[k], k, wc0, wc1);
+            if (holds) got += gf2_word_weight(a[k] ^ p[k], k, wc0, wc1);
           }
           if (got != want) {
             printf("ncols %d [%d, %d): weight %d over the words of the range, by bits %d\n", ncols, wc0, wc1, got, want);
@@ -60,7 +60,7 @@ int main() {
           ++ranges;
           for (int lanes : {1, 2, 8, 64})
             for (int vec = 0; vec < 2; ++vec) {
-              if (vec && nw < 2) continue;  // 16-byte accesses need a pair of words (join_rows_aligned16)
+              if (vec && nw < 2) continue;  // 16-byte accesses need a pair of words (gf2_rows_aligned16)
               int sum = 0;
               for (int sub = 0; sub < lanes; ++sub) sum += join_select_pair_weight(ha, hp, nw, vec, vec, sub, lanes, wc0, wc1);
               if (sum != want) {

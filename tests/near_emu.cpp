@@ -1,6 +1,6 @@
 // near_emu.cpp -- the word-level helpers of the Hamming-distance search (near_first_word, near_end_word, near_chunk_begin,
-// near_chunk_end, near_cell and near_plan of m4ri-rust_amd/csrc/near/near_plan.h; near_word_mask, near_in_window, near_excluded,
-// near_tile_class, near_pack_key, near_chunk_key, near_wide_key, near_key_dist, near_key_index, near_weight, near_row_weight and
+// near_chunk_end, near_cell and near_plan of m4ri-rust_amd/csrc/near/near_plan.h; gf2_word_mask of gf2_dev_words.h, which they use;
+// near_in_window, near_excluded, near_tile_class, near_pack_key, near_chunk_key, near_wide_key, near_key_dist, near_key_index, near_weight, near_row_weight and
 // near_tile_row of gf2_near.hip; cut out of the shipped files by tests/test_near_helpers_cpu.py) on the CPU under the host compiler's
 // address and undefined-behaviour sanitizers.
 //   the words and masks of a range: for every [wc0, wc1) of a row of ncols bits, [first, end) are exactly the words that hold a column
@@ -39,8 +39,8 @@ int tile_weights(const std::vector<u64> &a, const std::vector<u64> &p, int nw, i
   u64 am[W];
   for (int k = 0; k < W; ++k) {
     const bool in = k < end - first;
-    am[k] = in ? a[first + k] & near_word_mask(first + k, wc0, wc1) : 0;
-    for (int r = 0; r < rows; ++r) tile[r * W + k] = in && r == 1 ? p[first + k] & near_word_mask(first + k, wc0, wc1) : 0;
+    am[k] = in ? a[first + k] & gf2_word_mask(first + k, wc0, wc1) : 0;
+    for (int r = 0; r < rows; ++r) tile[r * W + k] = in && r == 1 ? p[first + k] & gf2_word_mask(first + k, wc0, wc1) : 0;
   }
   u64 b[W];
   near_tile_row<W>(tile, 1, b);
@@ -77,9 +77,9 @@ int main() {
             u64 m = 0;
             for (int c = wc0; c < wc1; ++c)
               if ((c >> 6) == k) m |= 1ull << (c & 63);
-            if (near_word_mask(k, wc0, wc1) != m) FAIL("ncols %d [%d, %d): the mask of word %lld", ncols, wc0, wc1, k);
+            if (gf2_word_mask(k, wc0, wc1) != m) FAIL("ncols %d [%d, %d): the mask of word %lld", ncols, wc0, wc1, k);
             if ((m != 0) != (k >= first && k < end)) FAIL("ncols %d [%d, %d): word %lld and [%lld, %lld)", ncols, wc0, wc1, k, first, end);
-            got += __popcll((a[k] ^ p[k]) & near_word_mask(k, wc0, wc1));
+            got += __popcll((a[k] ^ p[k]) & gf2_word_mask(k, wc0, wc1));
           }
           if (got != want) FAIL("ncols %d [%d, %d): weight %d over the masked words, by bits %d", ncols, wc0, wc1, got, want);
           if (near_row_weight(ha, hp, first, end, wc0, wc1) != want) FAIL("ncols %d [%d, %d): near_row_weight", ncols, wc0, wc1);

@@ -1,13 +1,11 @@
 // sums_emu.cpp -- the routines of the order of the subset sums (sums_max_c, sums_binomial, sums_rank, sums_unrank, sums_advance of
-// m4ri-rust_amd/csrc/sums/sums_plan.h) and the word weight of the kernel (sums_word_weight of m4ri-rust_amd/csrc/sums/gf2_sums.hip), cut
-// out of the shipped files by tests/test_sums_helpers_cpu.py, on the CPU under the host compiler's address and undefined-behaviour
-// sanitizers.
+// m4ri-rust_amd/csrc/sums/sums_plan.h), cut out of the shipped file by tests/test_sums_helpers_cpu.py, on the CPU under the host
+// compiler's address and undefined-behaviour sanitizers.  The word weight of the kernel is a shared helper: dev_words_emu.cpp.
 //   binomials: against Pascal's rule in 128-bit arithmetic, up to the largest c of every level.
 //   advance: for every p in 1 .. 4, n <= 14, every start rank and the strides 1, 2, 3, 64, 65, 1000, against `stride` single steps of a
 //   successor written out here, against sums_unrank of the sum of the ranks, and the carry flag against "c_2 .. c_p changed".
 //   unrank: around 2^31, 2^32 and 2^62 for every p, against sums_rank and against the neighbouring ranks (the successor of the
 //   subset of rank r - 1 is the subset of rank r); the rest that is left for a rank at or past C(n, p).
-//   the weight of a column range: as tests/join_emu.cpp does it for the join's copy.
 #include "kernel_emu.h"
 
 #define GF2_SUMS_FN inline
@@ -149,40 +147,6 @@ static long check_unrank_at_large_ranks() {
   return cases;
 }
 
-static long check_weights() {
-  const int widths[] = {1, 63, 64, 65, 130};
-  std::mt19937_64 rng(2027);
-  long cases = 0;
-  for (int ncols : widths) {
-    const int nw = (ncols + 63) >> 6;
-    for (int rep = 0; rep < 3; ++rep) {
-      std::vector<u64> row(nw);
-      for (int k = 0; k < nw; ++k) row[k] = rep == 0 ? rng() : rep == 1 ? ~0ull : (0xAAAAAAAAAAAAAAAAull >> (k & 1));
-      for (int wc0 = 0; wc0 <= ncols; ++wc0)
-        for (int wc1 = wc0; wc1 <= ncols; ++wc1) {
-          int want = 0;
-          for (int c = wc0; c < wc1; ++c) want += (int)((row[c >> 6] >> (c & 63)) & 1);
-          int got = 0;
-          for (int k = 0; k < nw; ++k) {
-            const bool holds = wc0 < wc1 && 64 * k < wc1 && wc0 < 64 * (k + 1);
-            const int w = sums_word_weight(row[k], k, wc0, wc1);
-            if (!holds && w != 0) {
-              printf("ncols %d [%d, %d): word %d is outside the range and counts %d\n", ncols, wc0, wc1, k, w);
-              return -1;
-            }
-            got += w;
-          }
-          if (got != want) {
-            printf("ncols %d [%d, %d): weight %d, by bits %d\n", ncols, wc0, wc1, got, want);
-            return -1;
-          }
-          ++cases;
-        }
-    }
-  }
-  return cases;
-}
-
 int main() {
   const long binomials = check_binomials();
   if (binomials < 0) return 1;
@@ -193,8 +157,5 @@ int main() {
   const long unranks = check_unrank_at_large_ranks();
   if (unranks < 0) return 1;
   printf("%ld unranks ok\n", unranks);
-  const long weights = check_weights();
-  if (weights < 0) return 1;
-  printf("%ld weights ok\n", weights);
   return 0;
 }

@@ -23,7 +23,9 @@ GATHER = os.path.join(ROOT, "m4ri-rust_amd", "csrc", "gather")
 FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 
 # what the program needs, in order: helper, kernel, launcher
-PIECES = ["gather_lo_hi", "gf2_gather_rows_kernel", "gf2k_gather_rows"]
+# the shared helpers of csrc/gf2_dev_words.h that they call: their text counts as the kernel's and the launcher's
+SHARED = ["gf2_lo_hi", "gf2_rows_aligned16"]
+PIECES = ["gf2_gather_rows_kernel", "gf2k_gather_rows"]
 # widths 6 x (D rows, S rows) 4 x (ld of D 3 x ld of S 3 x base of D 2 x base of S 2) x plain / accumulate x two index patterns
 EMULATED = {"gf2_gather_rows_kernel": ("gf2_gather_rows_kernel", 6 * 4 * 36 * 2 * 2)}
 NOT_EMULATED = {"gf2_gather_cols_kernel": "LDS, barriers, cross-lane"}
@@ -36,6 +38,11 @@ SIGNS = {
     "atomics": r"\batomic\w+\s*\(|__atomic_|__hip_atomic",
     "inline assembly": r"\basm\b",
 }
+
+
+def pieces_text():
+    words = os.path.join(ROOT, "m4ri-rust_amd", "csrc", "gf2_dev_words.h")
+    return kernel_text.extract_all(words, SHARED) + "\n" + kernel_text.extract_all(os.path.join(GATHER, "gf2_gather.hip"), PIECES)
 
 
 def sources():
@@ -68,7 +75,7 @@ def test_the_reasons_match_the_text():
     whole = kernel_text.mask(open(path).read())
     assert not re.search(SIGNS["inline assembly"], whole) and not re.search(SIGNS["atomics"], whole)   # the file uses neither at all
     for name in EMULATED:
-        text = kernel_text.mask(kernel_text.extract_all(path, PIECES))
+        text = kernel_text.mask(pieces_text())
         for word, sign in SIGNS.items():
             assert not re.search(sign, text), (name, word)
     for name, reason in NOT_EMULATED.items():
@@ -79,7 +86,7 @@ def test_the_reasons_match_the_text():
 
 def test_row_kernel_touches_only_words_of_its_operands(tmp_path):
     body = tmp_path / "gather_body.inc"
-    body.write_text(kernel_text.extract_all(os.path.join(GATHER, "gf2_gather.hip"), PIECES))
+    body.write_text(pieces_text())
     exe = tmp_path / "gather_emu"
     build = subprocess.run(["g++"] + FLAGS + ['-DKERNEL_BODY="%s"' % body, "-I", HERE, "-o", str(exe), os.path.join(HERE, "gather_emu.cpp")],
                            capture_output=True, text=True)

@@ -18,7 +18,8 @@ import kernel_text as kt
 HERE = os.path.dirname(os.path.abspath(__file__))
 JOIN = os.path.join(os.path.dirname(HERE), "m4ri-rust_amd", "csrc", "join")
 KERNEL, SELECT = os.path.join(JOIN, "gf2_join.hip"), os.path.join(JOIN, "gf2_join_select.inc")
-OLDER = ["join_word_weight", "join_lo_hi", "join_load2"]           # of gf2_join.hip, called by the new helpers
+WORDS = os.path.join(os.path.dirname(JOIN), "gf2_dev_words.h")
+SHARED = ["gf2_lo_hi", "gf2_load2", "gf2_word_weight"]             # of gf2_dev_words.h, called by the helpers
 HELPERS = ["join_select_first_word", "join_select_end_word", "join_select_is_hit", "join_select_pair_weight"]
 WIDTHS = (1, 63, 64, 65, 130)
 
@@ -29,7 +30,7 @@ def test_the_new_kernels_use_no_atomics_and_no_assembly():
     assert kt.global_kernels(SELECT) == ["gf2_join_weigh_kernel", "gf2_join_select_scatter_kernel"]
     # both kernels weigh and test a pair through the helpers alone, and gf2_join.hip includes the file once, inside its namespace
     assert shipped.count("join_select_pair_weight(") == 3 and shipped.count("join_select_is_hit(") == 3
-    assert shipped.count("__popcll(") == 2          # the ranking alone: a wave's hits, the hits before a group; weights go through join_word_weight
+    assert shipped.count("__popcll(") == 2          # the ranking alone: a wave's hits, the hits before a group; weights go through gf2_word_weight
     text = open(KERNEL).read()
     assert text.count('#include "gf2_join_select.inc"') == 1
     assert text.index('#include "gf2_join_select.inc"') < text.index("}  // namespace")
@@ -37,7 +38,7 @@ def test_the_new_kernels_use_no_atomics_and_no_assembly():
 
 def test_the_helpers_on_the_cpu(tmp_path):
     body = tmp_path / "join_select_body.inc"
-    body.write_text(kt.extract_all(KERNEL, OLDER) + "\n" + kt.extract_all(SELECT, HELPERS))
+    body.write_text(kt.extract_all(WORDS, SHARED) + "\n" + kt.extract_all(SELECT, HELPERS))
     text = body.read_text()
     for word in ("atomic", "__shfl", "__ballot", "__shared__", "__syncthreads", "threadIdx"):   # nothing a single CPU thread cannot run
         assert word not in text, word

@@ -3,7 +3,7 @@ host compiler's address and undefined-behaviour sanitizers (tests/near_emu.cpp),
 the weight-filtered join: the shipped text, cut out with tests/kernel_text.py, in a program of its own; near_plan.h is plain host
 arithmetic and is included as it is.
 
-  near_first_word / near_end_word / near_word_mask: the words and the bits of a range, over every range of ncols in {1, 63, 64, 65, 130}
+  near_first_word / near_end_word / gf2_word_mask (csrc/gf2_dev_words.h): the words and the bits of a range, over every range of ncols in {1, 63, 64, 65, 130}
   and a sample of those of 1100 columns; the masked popcounts sum to a bit-by-bit count.
   near_row_weight (the wide kernels) on rows in heap blocks of exactly the row's words; near_tile_row and near_weight (the register
   kernels) for W = 1, 2, 4, 8, 16 on every range that W words hold.
@@ -22,7 +22,8 @@ import kernel_text as kt
 HERE = os.path.dirname(os.path.abspath(__file__))
 NEAR = os.path.join(os.path.dirname(HERE), "m4ri-rust_amd", "csrc", "near")
 KERNEL, PLAN = os.path.join(NEAR, "gf2_near.hip"), os.path.join(NEAR, "near_plan.h")
-HELPERS = ["kNearNoKey", "kNearNoKey64", "near_word_mask", "near_in_window", "near_excluded", "near_tile_class", "near_pack_key", "near_chunk_key",
+WORDS = os.path.join(os.path.dirname(NEAR), "gf2_dev_words.h")
+HELPERS = ["kNearNoKey", "kNearNoKey64", "near_in_window", "near_excluded", "near_tile_class", "near_pack_key", "near_chunk_key",
            "near_wide_key", "near_key_dist", "near_key_index", "near_weight", "near_row_weight", "near_tile_row"]
 WIDTHS = (1, 63, 64, 65, 130)
 
@@ -33,6 +34,7 @@ def test_the_new_kernels_use_no_atomics_and_no_assembly():
     assert kt.global_kernels(KERNEL) == ["gf2_near_kernel", "gf2_near_wide_kernel", "gf2_near_scan_kernel", "gf2_near_fold_kernel"]
     # the kernels weigh, test and rank a pair through the helpers alone
     assert shipped.count("__popcll(") == 2                       # near_weight and near_row_weight
+    assert shipped.count("gf2_word_mask(") == 3                  # the masks of a range come from the shared helper: A, the tile, the wide rows
     assert shipped.count("near_in_window(") == 3 and shipped.count("near_excluded(") == 3 and shipped.count("near_pack_key(") == 2
     host = kt.mask(open(os.path.join(NEAR, "near_host.cpp")).read())
     assert "hipMalloc" not in host and "Synchronize" not in host
@@ -42,7 +44,7 @@ def test_the_new_kernels_use_no_atomics_and_no_assembly():
 
 def test_the_helpers_on_the_cpu(tmp_path):
     body = tmp_path / "near_body.inc"
-    body.write_text(kt.extract_all(KERNEL, HELPERS))
+    body.write_text(kt.extract(WORDS, "gf2_word_mask") + "\n" + kt.extract_all(KERNEL, HELPERS))
     text = body.read_text()
     for word in ("atomic", "__shfl", "__ballot", "__shared__", "__syncthreads", "threadIdx"):   # nothing a single CPU thread cannot run
         assert word not in text, word

@@ -23,7 +23,9 @@ WEIGHT = os.path.join(ROOT, "m4ri-rust_amd", "csrc", "weight")
 FLAGS = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 
 # what the program needs, in order: helpers, kernel, launcher
-PIECES = ["weight_lo_hi", "weight_row_partial", "gf2_weight_rows_narrow_kernel", "gf2k_weight_rows_narrow"]
+# the shared helpers of csrc/gf2_dev_words.h that they call: their text counts as the kernel's and the launcher's
+SHARED = ["gf2_lo_hi", "gf2_rows_aligned16"]
+PIECES = ["weight_row_partial", "gf2_weight_rows_narrow_kernel", "gf2k_weight_rows_narrow"]
 # widths 9 x rows 4 x (ld 3 x base 2) x content 3
 EMULATED = {"gf2_weight_rows_narrow_kernel": ("gf2_weight_rows_narrow_kernel", 9 * 4 * 6 * 3)}
 NOT_EMULATED = {
@@ -54,6 +56,11 @@ SIGNS = {
     "atomics": r"\batomic\w+\s*\(|__atomic_|__hip_atomic",
     "inline assembly": r"\basm\b",
 }
+
+
+def pieces_text():
+    words = os.path.join(ROOT, "m4ri-rust_amd", "csrc", "gf2_dev_words.h")
+    return kernel_text.extract_all(words, SHARED) + "\n" + kernel_text.extract_all(os.path.join(WEIGHT, "gf2_weight.hip"), PIECES)
 
 
 def sources():
@@ -90,7 +97,7 @@ def test_the_reasons_match_the_text():
     whole = kernel_text.mask(open(path).read())
     assert not re.search(SIGNS["inline assembly"], whole)   # builtins and plain C++ only
     for name in EMULATED:
-        text = kernel_text.mask(kernel_text.extract_all(path, PIECES))
+        text = kernel_text.mask(pieces_text())
         for word, sign in SIGNS.items():
             assert not re.search(sign, text), (name, word)
     for name, reason in NOT_EMULATED.items():
@@ -101,7 +108,7 @@ def test_the_reasons_match_the_text():
 
 def test_narrow_row_kernel_touches_only_words_of_its_operand(tmp_path):
     body = tmp_path / "weight_body.inc"
-    body.write_text(kernel_text.extract_all(os.path.join(WEIGHT, "gf2_weight.hip"), PIECES))
+    body.write_text(pieces_text())
     exe = tmp_path / "weight_emu"
     build = subprocess.run(["g++"] + FLAGS + ['-DKERNEL_BODY="%s"' % body, "-I", HERE, "-o", str(exe), os.path.join(HERE, "weight_emu.cpp")],
                            capture_output=True, text=True)
