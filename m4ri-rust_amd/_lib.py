@@ -179,43 +179,47 @@ _PROTOS = {
 # ctypes but are not part of the header check's mzd_* / gf2_* pattern)
 DECLARED_SYMBOLS = tuple(k for k in _PROTOS if not k.lower().startswith("mzp_"))
 
+# header under include/ -> its table.  lib() binds every table in here and the *_SYMBOLS tuples are read from here, so a table cannot
+# exist without being bound.
+_TABLES = {"m4ri_hip.h": _PROTOS}
+
 # what the companion header include/m4ri_hip_gather.h declares: a table of its own, so that DECLARED_SYMBOLS stays the list of
 # m4ri_hip.h (tests/test_gather_contract.py checks this header against the library)
-_GATHER_PROTOS = {
+_TABLES["m4ri_hip_gather.h"] = {
     "gf2_gather_rows_dev": (_I, [DMatP, DMatP, ctypes.c_void_p, _I, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_gather_cols_dev": (_I, [DMatP, DMatP, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_gather_cols_plan": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
 }
-GATHER_SYMBOLS = tuple(_GATHER_PROTOS)
+GATHER_SYMBOLS = tuple(_TABLES["m4ri_hip_gather.h"])
 
 # ... and include/m4ri_hip_weight.h (tests/test_weight_contract.py)
-_WEIGHT_PROTOS = {
+_TABLES["m4ri_hip_weight.h"] = {
     "gf2_row_weights_dev": (_I, [DMatP, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_col_weights_dev": (_I, [DMatP, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_count_ones_dev": (_I, [DMatP, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_select_weights_dev": (_I, [ctypes.c_void_p, _I, _I, _I, ctypes.c_void_p, _I, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_weights_plan": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
 }
-WEIGHT_SYMBOLS = tuple(_WEIGHT_PROTOS)
+WEIGHT_SYMBOLS = tuple(_TABLES["m4ri_hip_weight.h"])
 
 # ... and include/m4ri_hip_wht.h (tests/test_wht_contract.py)
-_WHT_PROTOS = {
+_TABLES["m4ri_hip_wht.h"] = {
     "gf2_lpn_tally_dev": (_I, [DMatP, _I, _I, _I, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_wht_dev": (_I, [ctypes.c_void_p, _I, ctypes.c_void_p]),
     "gf2_lpn_errors_dev": (_I, [DMatP, _I, _I, _I, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_min_weight_dev": (_I, [ctypes.c_void_p, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_wht_plan": (_I, [_I, ctypes.POINTER(ctypes.c_longlong)]),
 }
-WHT_SYMBOLS = tuple(_WHT_PROTOS)
+WHT_SYMBOLS = tuple(_TABLES["m4ri_hip_wht.h"])
 
 # ... and include/m4ri_hip_bkw.h (tests/test_bkw_contract.py)
 LF1_KEEP_ZERO = 1
-_BKW_PROTOS = {
+_TABLES["m4ri_hip_bkw.h"] = {
     "gf2_class_first_dev": (_I, [DMatP, _I, _I, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_lf1_reduce_dev": (_I, [DMatP, DMatP, _I, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_lf1_plan": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
 }
-BKW_SYMBOLS = tuple(_BKW_PROTOS)
+BKW_SYMBOLS = tuple(_TABLES["m4ri_hip_bkw.h"])
 
 # ... and include/m4ri_hip_cover.h (tests/test_cover_contract.py)
 COVER_MAX_N, COVER_MAX_R, COVER_MAX_CODES, COVER_MAX_SEGS, COVER_MAX_LEADERS = 32, 12, 16, 256, 16384
@@ -230,25 +234,25 @@ class CoverCodeStruct(ctypes.Structure):
 assert ctypes.sizeof(CoverCodeStruct) == 56
 
 CoverCodeP = ctypes.POINTER(CoverCodeStruct)
-_COVER_PROTOS = {
+_TABLES["m4ri_hip_cover.h"] = {
     "gf2_cover_code_named": (_I, [_I, _I, CoverCodeP]),
     "gf2_cover_leaders": (_I, [CoverCodeP, ctypes.c_void_p, ctypes.POINTER(_I)]),
     "gf2_cover_reduce_dev": (_I, [DMatP, DMatP, _I, CoverCodeP, _I, ctypes.c_void_p, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_cover_plan": (_I, [_I, _I, CoverCodeP, _I, ctypes.c_void_p, _I, ctypes.POINTER(ctypes.c_longlong)]),
 }
-COVER_SYMBOLS = tuple(_COVER_PROTOS)
+COVER_SYMBOLS = tuple(_TABLES["m4ri_hip_cover.h"])
 
 # ... and include/m4ri_hip_lf2.h (tests/test_lf2_contract.py)
-_LF2_PROTOS = {
+_TABLES["m4ri_hip_lf2.h"] = {
     "gf2_class_sort_dev": (_I, [DMatP, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_lf2_reduce_dev": (_I, [DMatP, DMatP, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_lf2_plan": (_I, [_I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
 }
-LF2_SYMBOLS = tuple(_LF2_PROTOS)
+LF2_SYMBOLS = tuple(_TABLES["m4ri_hip_lf2.h"])
 
 # ... and include/m4ri_hip_draw.h (tests/test_draw_contract.py)
 DRAW_BERNOULLI, DRAW_INDICES, DRAW_SUBSETS, DRAW_PERMUTATION = 1, 2, 3, 4
-_DRAW_PROTOS = {
+_TABLES["m4ri_hip_draw.h"] = {
     "gf2_bernoulli_dev": (_I, [DMatP, ctypes.c_uint32, ctypes.c_uint64, _I, ctypes.c_void_p]),
     "gf2_bernoulli_block_dev": (_I, [DMatP, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, _I, _I, ctypes.c_void_p]),
     "gf2_draw_indices_dev": (_I, [ctypes.c_void_p, ctypes.c_longlong, _I, ctypes.c_uint64, ctypes.c_void_p]),
@@ -256,18 +260,18 @@ _DRAW_PROTOS = {
     "gf2_draw_permutation_dev": (_I, [ctypes.c_void_p, _I, ctypes.c_uint64, ctypes.c_void_p]),
     "gf2_draw_plan": (_I, [_I, ctypes.c_longlong, _I, ctypes.c_uint32, ctypes.POINTER(ctypes.c_longlong)]),
 }
-DRAW_SYMBOLS = tuple(_DRAW_PROTOS)
+DRAW_SYMBOLS = tuple(_TABLES["m4ri_hip_draw.h"])
 
 # ... and include/m4ri_hip_join.h (tests/test_join_contract.py)
-_JOIN_PROTOS = {
+_TABLES["m4ri_hip_join.h"] = {
     "gf2_join_dev": (_I, [DMatP, DMatP, DMatP, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _I, _I,
                           ctypes.c_void_p]),
     "gf2_join_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
 }
-JOIN_SYMBOLS = tuple(_JOIN_PROTOS)
+JOIN_SYMBOLS = tuple(_TABLES["m4ri_hip_join.h"])
 
 # ... and include/m4ri_hip_sums.h (tests/test_sums_contract.py)
-_SUMS_PROTOS = {
+_TABLES["m4ri_hip_sums.h"] = {
     "gf2_subset_sums_dev": (_I, [DMatP, DMatP, DMatP, _I, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, _I, _I, ctypes.c_void_p]),
     "gf2_unrank_subsets_dev": (_I, [ctypes.c_void_p, _I, ctypes.c_longlong, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_subset_count": (ctypes.c_longlong, [_I, _I]),
@@ -275,24 +279,24 @@ _SUMS_PROTOS = {
     "gf2_subset_unrank": (_I, [ctypes.c_longlong, _I, ctypes.POINTER(_I)]),
     "gf2_subset_sums_plan": (_I, [_I, _I, _I, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]),
 }
-SUMS_SYMBOLS = tuple(_SUMS_PROTOS)
+SUMS_SYMBOLS = tuple(_TABLES["m4ri_hip_sums.h"])
 
 # ... and include/m4ri_hip_join_select.h (tests/test_join_select_contract.py)
-_JOIN_SELECT_PROTOS = {
+_TABLES["m4ri_hip_join_select.h"] = {
     "gf2_join_select_dev": (_I, [DMatP, DMatP, DMatP, _I, _I, _I, _I, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_join_select_plan": (_I, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
 }
-JOIN_SELECT_SYMBOLS = tuple(_JOIN_SELECT_PROTOS)
+JOIN_SELECT_SYMBOLS = tuple(_TABLES["m4ri_hip_join_select.h"])
 
 # ... and include/m4ri_hip_near.h (tests/test_near_contract.py)
-_NEAR_PROTOS = {
+_TABLES["m4ri_hip_near.h"] = {
     "gf2_near_pairs_dev": (_I, [DMatP, DMatP, DMatP, _I, _I, _I, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.c_void_p]),
     "gf2_nearest_dev": (_I, [DMatP, DMatP, _I, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "gf2_near_plan": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
 }
-NEAR_SYMBOLS = tuple(_NEAR_PROTOS)
+NEAR_SYMBOLS = tuple(_TABLES["m4ri_hip_near.h"])
 
 _lib = None
 
@@ -306,9 +310,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C m4ri-rust_amd/csrc`). There is no fallback for the HIP multiply path.")
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        tables = (_PROTOS, _GATHER_PROTOS, _WEIGHT_PROTOS, _WHT_PROTOS, _BKW_PROTOS, _COVER_PROTOS, _LF2_PROTOS, _DRAW_PROTOS, _JOIN_PROTOS,
-                  _SUMS_PROTOS, _JOIN_SELECT_PROTOS, _NEAR_PROTOS)
-        for name, (res, args) in [item for table in tables for item in table.items()]:
+        for name, (res, args) in [item for table in _TABLES.values() for item in table.items()]:
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

@@ -2,6 +2,26 @@
 
 `DMat` owns (or wraps) a dense bit matrix in HBM: row-major 64-bit words, LSB-first, `ld` words
 per row.  Used by bench.py, the multi-GPU layer and tests that must not pay PCIe per product.
+
+Output arrays
+-------------
+The wrappers of the companion headers (include/m4ri_hip_*.h) write int arrays next to their matrices.  Every such argument is
+  * a raw device address (e.g. a torch int32 / int64 tensor's data_ptr()): the kernels write there, None is returned in its place;
+  * SKIP (0), where the wrapper's docstring allows it: the array is not wanted, the C call gets NULL, None is returned in its place;
+  * None (the default): the wrapper allocates the array itself.
+What None returns depends on the wrapper, and its docstring says which kind it is:
+  * a wrapper that WAITS for `stream` returns the values: a numpy int32 array, or an int / a bool for a single value.  Such a
+    wrapper only enqueues on `stream` when none of its arrays is None;
+  * a wrapper that only enqueues returns the array as an object with .ptr (its device address, which feeds the next wrapper as it
+    is), .read(stream) (numpy; waits for `stream`), .count (the int32s it holds) and .mat (the DMat behind it).  An array of no
+    element is None, except where the docstring says that the object is always there.
+An input array (`idx`, `weights`, `ranks`, ...) is a raw device address or a list / numpy int array that the wrapper uploads.
+
+Count first: where a wrapper stores one row of D per pair or hit, the capacity is D.nrows, else `cap`, and `count` / `hits` say how
+many there are in all, which may be more; the call then only enqueues.  With neither D nor cap a count-only call comes first, the
+wrapper WAITS for it and sizes D to exactly that many rows (ValueError for 2^31 rows or more, and for a raw `count` / `hits` address,
+which the wrapper cannot read).  store=False: the rows are not stored -- D is passed without data, None is returned in its place and
+only the arrays are written (the index-only mode); it takes no D.
 """
 import ctypes
 
@@ -320,83 +340,154 @@ def inverse(A, stream=None):
     return None if singular.value else out
 
 
-class _IntScratch:
-    """`count` device ints for a call that was given no array of its own: a dense DMat of 128 ints per row."""
+SKIP = 0  # for an output array that accepts it: do not compute it (the C call gets NULL)
 
-    def __init__(self, count):
-        self.count = count
-        self.mat = DMat((count + 127) // 128, 4096)
+
+# ---- the one copy of the rules of "Output arrays" (module docstring) ----------------------------------------------------------------
+
+class _Ints:
+    """Device ints that a wrapper owns, in a dense DMat of 128 int32 per row: `count` elements of `dtype` (int32 or int64), each a
+    tuple of `width` of them if given (read() then has shape (count, width)); or, with `values`, host ints uploaded on `stream` (at
+    least one row).  `least`: room for that many int32 even where count is smaller.  .count is in int32s."""
+
+    def __init__(self, count=0, dtype=np.int32, width=None, values=None, least=0, stream=None):
+        self.dtype, self.width = dtype, width
+        if values is None:
+            self.count = count * (width or 1) * (np.dtype(dtype).itemsize // 4)
+            self.mat = DMat((max(self.count, least) + 127) // 128, 4096)
+        else:
+            v = np.ascontiguousarray(np.asarray(values).reshape(-1), dtype=np.int32)
+            self.count = len(v)
+            rows = max((self.count + 127) // 128, 1)
+            full = np.zeros(rows * 128, dtype=np.int32)
+            full[:self.count] = v
+            self.mat = DMat.from_words(full.view(np.uint64).reshape(rows, 64), 4096, stream)
 
     @property
     def ptr(self):
         return self.mat.s.data
 
     def read(self, stream):
-        """the ints as a numpy array; waits for `stream`"""
+        """the values as a numpy array; waits for `stream`"""
         self.mat._streams.add(stream)
-        return np.ascontiguousarray(self.mat.to_words(stream)).reshape(-1).view(np.int32)[:self.count].copy()
+        a = np.ascontiguousarray(self.mat.to_words(stream)).reshape(-1).view(np.int32)[:self.count].copy().view(self.dtype)
+        return a if self.width is None else a.reshape(-1, self.width)
+
+
+def _out(given, count, always=False, **kind):
+    """An output argument -> (pointer for the C call, the array the wrapper owns or None).  `given`: None, a raw address or SKIP.
+    An own array is allocated only for count > 0; always: in any case, with room for one int (an address even for no element)."""
+    if given is not None:
+        return given or None, None
+    if count <= 0 and not always:
+        return None, None
+    own = _Ints(count, least=int(always), **kind)
+    return own.ptr, own
+
+
+def _outs(givens, count, always=False):
+    """_out for several int32 arrays of one length -> (pointers, owned)"""
+    pairs = [_out(given, count, always) for given in givens]
+    return [p for p, _ in pairs], [own for _, own in pairs]
+
+
+def _used(stream, *owned):
+    """after a call that passed _lib.check: its own arrays are in use on `stream` (and are released in its order)"""
+    for own in owned:
+        if own:
+            own.mat._streams.add(stream)
+
+
+def _numpy(given, own, stream):
+    """what a wrapper that WAITS returns for an output array: None in the place of the caller's own, else the values"""
+    if given is not None:
+        return None
+    return own.read(stream) if own else np.zeros(0, dtype=np.int32)
+
+
+def _one_array(name, call, given, count, stream, wait, always=False):
+    """a wrapper with one int32 output array: call(pointer) -> rc"""
+    ptr, own = _out(given, count, always)
+    _lib.check(call(ptr), name)
+    if wait:
+        return _numpy(given, own, stream)
+    _used(stream, own)
+    return own
+
+
+def _count_first(name, what, own, count_only, stream, fits=True):
+    """The capacity of a D that is sized by a count-only call: count_only() makes it, `own` is the wrapper's array of the count of
+    `what` ("pairs": the argument `count`; "hits": `hits`); WAITS for `stream`.  fits: a D of 2^31 rows or more is refused."""
+    arg = "hits" if what == "hits" else "count"
+    if own is None:
+        raise ValueError("%s: a raw %s address needs D or cap (the wrapper cannot read the %s to size D)" % (name, arg, arg))
+    count_only()
+    cap = int(own.read(stream)[0])
+    if fits and cap >= 1 << 31:
+        raise ValueError("%s: %d %s do not fit a matrix; give D or cap" % (name, cap, what))
+    return cap
+
+
+def _unstored(nrows, ncols):
+    """the D of store=False: rows without data"""
+    return DMat.wrap(None, nrows, ncols, max((ncols + 63) // 64, 1))
+
+
+def _bad_int(bad, stream):
+    """the `bad` argument -> (pointer, the zeroed int the wrapper owns or None)"""
+    if bad is not None:
+        return bad or None, None
+    own = _Ints(values=[0], stream=stream)
+    return own.ptr, own
+
+
+def _bad_result(own, stream):
+    return bool(own.read(stream)[0]) if own else None
+
+
+def _plan(fn, args, n, lead=True):
+    """a plan query fn(*args, out[n]) -> a tuple of ints, the return value first if `lead`; None for a negative return value"""
+    out = (ctypes.c_longlong * n)()
+    v = fn(*args, out)
+    if v < 0:
+        return None
+    return ((int(v),) if lead else ()) + tuple(int(x) for x in out)
+
+
+def _wcols(ncols, wcols):
+    return (0, ncols) if wcols is None else wcols
 
 
 def elim_batch_plan(m, ncols, inverse=False):
     """Which kernel a batch of m x ncols matrices runs on (no device needed) -> (variant id, threads per workgroup, matrices per
     workgroup, LDS bytes per workgroup, words per row held), or None when the shape is outside the limits."""
-    out = (ctypes.c_longlong * 4)()
-    v = _lib.lib().gf2_elim_batch_plan(m, ncols, int(bool(inverse)), out)
-    return None if v < 0 else (v, out[0], out[1], out[2], out[3])
-
-
-SKIP = 0  # for an output array of echelonize_batch / inverse_batch: do not compute it (the C call gets NULL)
+    return _plan(_lib.lib().gf2_elim_batch_plan, (m, ncols, int(bool(inverse))), 4)
 
 
 def echelonize_batch(A, m, full=True, ncols_limit=0, ranks=None, pivots=None, stream=None):
     """Every m-row matrix of the stack A (matrix b = rows [b*m, (b+1)*m)) is replaced by its echelon form, each as echelonize() would
-    leave it.  -> (ranks, pivots).  Each of `ranks` (batch int32) and `pivots` (batch * P int32, P = min(m, limit), padded with -1) is
-      * a raw device address, e.g. a torch int32 tensor's data_ptr(): the kernel writes there, None is returned in its place;
-      * SKIP (0): the array is not wanted, None is returned in its place;
-      * None (the default): the wrapper allocates scratch, WAITS for `stream` and returns a numpy array (pivots: shape (batch, P)).
-    The call only enqueues on `stream` and returns -- asynchronous -- when neither argument is None."""
+    leave it.  -> (ranks, pivots): `ranks` batch int32, `pivots` batch * P int32, P = min(m, limit), padded with -1 (numpy: shape
+    (batch, P)).  Either may be SKIP.  WAITS."""
     batch = A.nrows // m if m > 0 else 0
     limit = ncols_limit if 0 < ncols_limit < A.ncols else A.ncols
     P = max(min(m, limit), 0)
-    own_r = _IntScratch(batch) if ranks is None and batch > 0 else None
-    own_p = _IntScratch(batch * P) if pivots is None and batch * P > 0 else None
-    _lib.check(_lib.lib().gf2_echelonize_batch_dev(A._on(stream), m, int(bool(full)), int(ncols_limit),
-                                                   own_r.ptr if own_r else ranks, own_p.ptr if own_p else pivots, stream),
+    rptr, own_r = _out(ranks, batch)
+    pptr, own_p = _out(pivots, batch * P)
+    _lib.check(_lib.lib().gf2_echelonize_batch_dev(A._on(stream), m, int(bool(full)), int(ncols_limit), rptr, pptr, stream),
                "gf2_echelonize_batch_dev")
-    out_r = out_p = None
-    if ranks is None:
-        out_r = own_r.read(stream) if own_r else np.zeros(0, dtype=np.int32)
-    if pivots is None:
-        out_p = (own_p.read(stream) if own_p else np.zeros(0, dtype=np.int32)).reshape(batch, P)
-    return out_r, out_p
+    out_r, out_p = _numpy(ranks, own_r, stream), _numpy(pivots, own_p, stream)
+    return out_r, out_p if out_p is None else out_p.reshape(batch, P)
 
 
 def inverse_batch(A, n, Ainv=None, singular=None, stream=None):
     """Block b of Ainv = (block b of A)^-1 for the n x n blocks of the stack A; blocks without an inverse are flagged in `singular`
-    and left as they were in Ainv (a fresh Ainv: undefined).  -> (Ainv, singular).  `singular` (batch int32) is a raw device address or
-    SKIP (0) -- the call then only enqueues on `stream`, None is returned in its place -- or None: the wrapper allocates scratch, WAITS
-    for `stream` and returns a numpy array."""
+    and left as they were in Ainv (a fresh Ainv: undefined).  -> (Ainv, singular): `singular` batch int32, may be SKIP.  WAITS."""
     if Ainv is None:
         Ainv = DMat(A.nrows, A.ncols)
     batch = A.nrows // n if n > 0 else 0
-    own = _IntScratch(batch) if singular is None and batch > 0 else None
-    _lib.check(_lib.lib().gf2_inverse_batch_dev(Ainv._on(stream), A._on(stream), n, own.ptr if own else singular, stream),
-               "gf2_inverse_batch_dev")
-    if singular is not None:
-        return Ainv, None
-    return Ainv, own.read(stream) if own else np.zeros(0, dtype=np.int32)
-
-
-class _IntUpload(_IntScratch):
-    """host ints as a device array, through device words like _IntScratch: 128 ints per row of a dense DMat"""
-
-    def __init__(self, values, stream=None):
-        v = np.ascontiguousarray(np.asarray(values).reshape(-1), dtype=np.int32)
-        self.count = len(v)
-        rows = max((self.count + 127) // 128, 1)
-        full = np.zeros(rows * 128, dtype=np.int32)
-        full[:self.count] = v
-        self.mat = DMat.from_words(full.view(np.uint64).reshape(rows, 64), 4096, stream)
+    sptr, own = _out(singular, batch)
+    _lib.check(_lib.lib().gf2_inverse_batch_dev(Ainv._on(stream), A._on(stream), n, sptr, stream), "gf2_inverse_batch_dev")
+    return Ainv, _numpy(singular, own, stream)
 
 
 def _device_ints(idx, count, what, stream):
@@ -410,31 +501,26 @@ def _device_ints(idx, count, what, stream):
         return None, None
     if arr.dtype.kind not in "iu" or arr.min() < -(1 << 31) or arr.max() >= (1 << 31):
         raise ValueError("%s: idx must hold int32 values" % what)
-    up = _IntUpload(arr, stream)
+    up = _Ints(values=arr, stream=stream)
     return up.ptr, up
 
 
 def _gather(name, D, S, ptr, accumulate, bad, stream):
-    own = None
-    if bad is None:
-        own = _IntUpload([0], stream)
-        bad = own.ptr
+    bptr, own = _bad_int(bad, stream)
     L = _lib.lib()
     if name == "gf2_gather_rows_dev":
-        rc = L.gf2_gather_rows_dev(D._on(stream), S._on(stream), ptr, int(bool(accumulate)), bad or None, stream)
+        rc = L.gf2_gather_rows_dev(D._on(stream), S._on(stream), ptr, int(bool(accumulate)), bptr, stream)
     else:
-        rc = L.gf2_gather_cols_dev(D._on(stream), S._on(stream), ptr, bad or None, stream)
+        rc = L.gf2_gather_cols_dev(D._on(stream), S._on(stream), ptr, bptr, stream)
     _lib.check(rc, name)
-    return D, (bool(own.read(stream)[0]) if own else None)
+    return D, _bad_result(own, stream)
 
 
 def gather_rows(S, idx, D=None, accumulate=False, bad=SKIP, stream=None):
     """D[i] (^)= S[idx[i]] for every row i of D (default: a new len(idx) x S.ncols matrix) -> (D, bad).  An index of -1 gives a zero row
-    (accumulate: leaves the row), any other value outside S's rows likewise and is reported in `bad`.  `idx` is a raw device address of
-    D.nrows int32 (e.g. a torch int32 tensor's data_ptr()) or a list / numpy int array that the wrapper uploads.  `bad` follows
-    `singular` of inverse_batch(): a raw device address of an int the caller has zeroed, or SKIP (0) -- the call then only enqueues on
-    `stream` and None is returned in its place -- or None: the wrapper allocates a zeroed int, WAITS for `stream` and returns a bool.
-    Duplicates are fine; D may share no word with S (HipError, "overlap")."""
+    (accumulate: leaves the row), any other value outside S's rows likewise and is reported in `bad`.  `idx`: D.nrows int32, an input
+    array.  `bad`: one int32 that a caller who gives its address has zeroed; SKIP is the default; None: the wrapper zeroes an int of its
+    own, WAITS and returns a bool.  Duplicates are fine; D may share no word with S (HipError, "overlap")."""
     if D is None:
         if isinstance(idx, (int, np.integer)):
             raise ValueError("gather_rows: a raw idx address needs D (its row count is the number of indices)")
@@ -457,9 +543,7 @@ def gather_cols(S, idx, D=None, bad=SKIP, stream=None):
 def gather_cols_plan(nrows, s_ncols, d_ncols):
     """Which path a column gather of this shape takes (no device needed) -> (path, threads per workgroup, LDS bytes per workgroup, rows
     per workgroup, scratch bytes) with path 0 = the fused LDS kernel, 1 = transpose / row gather / transpose; None for a bad shape."""
-    out = (ctypes.c_longlong * 4)()
-    path = _lib.lib().gf2_gather_cols_plan(nrows, s_ncols, d_ncols, out)
-    return None if path < 0 else (path, out[0], out[1], out[2], out[3])
+    return _plan(_lib.lib().gf2_gather_cols_plan, (nrows, s_ncols, d_ncols), 4)
 
 
 _WEIGHT_WHAT = {"rows": 0, "cols": 1, "columns": 1, "total": 2}
@@ -469,62 +553,47 @@ def weights_plan(what, nrows, ncols):
     """Which kernel the weights of an nrows x ncols matrix run on (no device needed); what: "rows", "cols" or "total" (0, 1, 2)
     -> (variant id, threads per workgroup, rows per workgroup and pass, rows a lane takes before it empties its bit-sliced counters
     (columns; else 0), scratch bytes); None for a bad shape.  The variant ids are listed in include/m4ri_hip_weight.h."""
-    out = (ctypes.c_longlong * 4)()
-    v = _lib.lib().gf2_weights_plan(_WEIGHT_WHAT.get(what, what), nrows, ncols, out)
-    return None if v < 0 else (v, out[0], out[1], out[2], out[3])
-
-
-def _weights(name, A, count, out, stream):
-    own = _IntScratch(count) if out is None and count > 0 else None
-    rc = getattr(_lib.lib(), name)(A._on(stream), own.ptr if own else out, stream)
-    _lib.check(rc, name)
-    if out is not None:
-        return None
-    return own.read(stream) if own else np.zeros(0, dtype=np.int32)
+    return _plan(_lib.lib().gf2_weights_plan, (_WEIGHT_WHAT.get(what, what), nrows, ncols), 4)
 
 
 def row_weights(A, out=None, stream=None):
-    """The Hamming weight of every row of A.  `out` is a raw device address of A.nrows int32 (e.g. a torch int32 tensor's data_ptr()):
-    the call only enqueues on `stream` and None is returned; or None: the wrapper allocates scratch, WAITS for `stream` and returns a
-    numpy int32 array.  Only A's ncols bits count; the array is overwritten, the caller zeroes nothing."""
-    return _weights("gf2_row_weights_dev", A, A.nrows, out, stream)
+    """The Hamming weight of every row of A: `out`, A.nrows int32.  WAITS.  Only A's ncols bits count; the array is overwritten, the
+    caller zeroes nothing."""
+    L = _lib.lib()
+    return _one_array("gf2_row_weights_dev", lambda p: L.gf2_row_weights_dev(A._on(stream), p, stream), out, A.nrows, stream, True)
 
 
 def col_weights(A, out=None, stream=None):
-    """The number of rows of A with bit j set, for every column j (A.ncols int32); `out` as in row_weights().  weights_plan("cols", ...)
+    """The number of rows of A with bit j set, for every column j: `out`, A.ncols int32, as in row_weights().  weights_plan("cols", ...)
     tells how the rows are cut into bands."""
-    return _weights("gf2_col_weights_dev", A, A.ncols, out, stream)
+    L = _lib.lib()
+    return _one_array("gf2_col_weights_dev", lambda p: L.gf2_col_weights_dev(A._on(stream), p, stream), out, A.ncols, stream, True)
 
 
 def count_ones(A, stream=None):
     """The number of set bits of A as a Python int (nrows * ncols can pass 2^32); WAITS for `stream`."""
-    own = _IntScratch(2)
+    own = _Ints(2)   # one uint64
     _lib.check(_lib.lib().gf2_count_ones_dev(A._on(stream), own.ptr, stream), "gf2_count_ones_dev")
     return int(own.read(stream).view(np.uint64)[0])
 
 
 def select_weights(weights, n, lo, hi, idx=None, cap=None, count=None, stream=None):
-    """The indices i < n with lo <= weights[i] <= hi, ascending -> (idx, count).  `weights` is a raw device address of n int32 (what
-    row_weights / col_weights wrote) or a list / numpy int array that the wrapper uploads.  At most `cap` (default: n) indices are
-    stored; `count` is how many there are in all and may exceed cap.  Each of `idx` (cap int32) and `count` (one int32) is a raw device
-    address -- the kernel writes there, None is returned in its place -- or None: the wrapper allocates scratch, WAITS for `stream`
-    and returns numpy (idx cut to min(count, cap) when the wrapper owns the count too) / an int.  idx=SKIP (0) is a count-only call.
-    The device array idx feeds gather_rows / gather_cols as it is."""
+    """The indices i < n with lo <= weights[i] <= hi, ascending -> (idx, count).  `weights`: n int32, an input array (what row_weights /
+    col_weights wrote).  At most `cap` (default: n) indices are stored; `count` is how many there are in all and may exceed cap.
+    `idx`: cap int32 (numpy: cut to min(count, cap) when the wrapper owns the count too); `count`: one int32 (an int).  WAITS.
+    idx=SKIP is a count-only call.  The device array idx feeds gather_rows / gather_cols as it is."""
     if cap is None:
         cap = n
     if idx is not None and idx == SKIP:
         cap = 0
     wptr, keep = _device_ints(weights, n, "select_weights", stream)
-    own_i = _IntScratch(cap) if idx is None and cap > 0 else None
-    own_c = _IntScratch(1) if count is None else None
-    rc = _lib.lib().gf2_select_weights_dev(wptr, n, lo, hi, own_i.ptr if own_i else (idx or None), cap, own_c.ptr if own_c else count, stream)
-    _lib.check(rc, "gf2_select_weights_dev")
+    iptr, own_i = _out(idx, cap)
+    cptr, own_c = _out(count, 1)
+    _lib.check(_lib.lib().gf2_select_weights_dev(wptr, n, lo, hi, iptr, cap, cptr, stream), "gf2_select_weights_dev")
     out_c = int(own_c.read(stream)[0]) if own_c and (n > 0 or cap > 0) else (0 if own_c else None)
-    out_i = None
-    if idx is None:
-        out_i = own_i.read(stream) if own_i else np.zeros(0, dtype=np.int32)
-        if out_c is not None:
-            out_i = out_i[:min(out_c, cap)]
+    out_i = _numpy(idx, own_i, stream)
+    if out_i is not None and out_c is not None:
+        out_i = out_i[:min(out_c, cap)]
     return out_i, out_c
 
 
@@ -537,18 +606,11 @@ def wht_plan(k):
     return None if passes < 0 else (passes, [int(out[p]) for p in range(passes)] + [k], out[8], out[9], out[10], out[11])
 
 
-def _wht_array(name, call, count, out, stream):
-    own = _IntScratch(count) if out is None else None
-    _lib.check(call(own.ptr if own else out), name)
-    return own.read(stream) if own else None
-
-
 def lpn_tally(P, c0, k, label_col=-1, out=None, stream=None):
     """f[v] = (rows of P whose bits [c0, c0 + k) read v and whose bit label_col is 0) - (... is 1), v < 2^k; label_col = -1: the plain
-    histogram.  `out` is a raw device address of 2^k int32 (e.g. a torch int32 tensor's data_ptr()): the call only enqueues on `stream`
-    and None is returned; or None: the wrapper allocates scratch, WAITS for `stream` and returns a numpy int32 array."""
+    histogram.  `out`: 2^k int32.  WAITS."""
     L = _lib.lib()
-    return _wht_array("gf2_lpn_tally_dev", lambda p: L.gf2_lpn_tally_dev(P._on(stream), c0, k, label_col, p, stream), 1 << k, out, stream)
+    return _one_array("gf2_lpn_tally_dev", lambda p: L.gf2_lpn_tally_dev(P._on(stream), c0, k, label_col, p, stream), out, 1 << k, stream, True)
 
 
 def wht(f, k, stream=None):
@@ -568,18 +630,16 @@ def lpn_errors(P, c0, k, label_col, out=None, stream=None):
     gives for S = all 2^k vectors.  `out` as in lpn_tally() (16-byte aligned when k >= 2); the array feeds select_weights / min_weight
     as it is."""
     L = _lib.lib()
-    return _wht_array("gf2_lpn_errors_dev", lambda p: L.gf2_lpn_errors_dev(P._on(stream), c0, k, label_col, p, stream), 1 << k, out, stream)
+    return _one_array("gf2_lpn_errors_dev", lambda p: L.gf2_lpn_errors_dev(P._on(stream), c0, k, label_col, p, stream), out, 1 << k, stream, True)
 
 
 def min_weight(w, n, idx=None, val=None, stream=None):
-    """The smallest of w[0 .. n) and the LOWEST index that holds it -> (idx, val).  `w` is a raw device address of n int32 or a list /
-    numpy int array that the wrapper uploads.  Each of `idx` and `val` is a raw device address of one int32 -- the kernel writes there,
-    None is returned in its place -- or None: the wrapper allocates scratch, WAITS for `stream` and returns an int."""
+    """The smallest of w[0 .. n) and the LOWEST index that holds it -> (idx, val).  `w`: n int32, an input array.  `idx`, `val`: one
+    int32 each (an int).  WAITS."""
     wptr, keep = _device_ints(w, n, "min_weight", stream)
-    own_i = _IntScratch(1) if idx is None else None
-    own_v = _IntScratch(1) if val is None else None
-    rc = _lib.lib().gf2_min_weight_dev(wptr, n, own_i.ptr if own_i else idx, own_v.ptr if own_v else val, stream)
-    _lib.check(rc, "gf2_min_weight_dev")
+    iptr, own_i = _out(idx, 1)
+    vptr, own_v = _out(val, 1)
+    _lib.check(_lib.lib().gf2_min_weight_dev(wptr, n, iptr, vptr, stream), "gf2_min_weight_dev")
     return (int(own_i.read(stream)[0]) if own_i else None), (int(own_v.read(stream)[0]) if own_v else None)
 
 
@@ -587,47 +647,36 @@ def lf1_plan(nrows, ncols, b):
     """How an LF1 round over nrows x ncols with a window of b bits runs (no device needed) -> (variant of the class-first kernel (0:
     table in LDS, 1: global atomics), its threads per workgroup, its LDS bytes, rows a workgroup of the count / scatter kernels covers,
     lanes per row of the scatter kernel, scratch bytes); None for a bad shape."""
-    out = (ctypes.c_longlong * 5)()
-    v = _lib.lib().gf2_lf1_plan(nrows, ncols, b, out)
-    return None if v < 0 else (v, out[0], out[1], out[2], out[3], out[4])
+    return _plan(_lib.lib().gf2_lf1_plan, (nrows, ncols, b), 5)
 
 
 def class_first(P, c0, b, out=None, stream=None):
-    """first[v] = the lowest row of P whose bits [c0, c0 + b) read v, -1 where no row does, v < 2^b.  `out` is a raw device address of
-    2^b int32: the call only enqueues on `stream` and None is returned; or None: the wrapper allocates scratch, WAITS for `stream` and
-    returns a numpy int32 array."""
+    """first[v] = the lowest row of P whose bits [c0, c0 + b) read v, -1 where no row does, v < 2^b.  `out`: 2^b int32.  WAITS."""
     L = _lib.lib()
-    return _wht_array("gf2_class_first_dev", lambda p: L.gf2_class_first_dev(P._on(stream), c0, b, p, stream), 1 << b, out, stream)
+    return _one_array("gf2_class_first_dev", lambda p: L.gf2_class_first_dev(P._on(stream), c0, b, p, stream), out, 1 << b, stream, True)
 
 
 def lf1_reduce(P, c0, b, keep_zero=False, D=None, cap=None, first=None, count=None, src=None, stream=None):
     """One LF1 round of a BKW reduction (include/m4ri_hip_bkw.h): the rows of P are partitioned by their bits [c0, c0 + b), the first
     row of every class is XORed into the other rows of its class and dropped; with keep_zero the rows of key 0 stay as they are.
-    -> (D, count, first, src), all on the device: D holds the survivors in their order (D.nrows is the capacity; `count` says how many
-    there are in all), first[v] the first row of class v (2^b int32), src[j] the row of P that D[j] came from.  Each of `first`,
-    `count` and `src` is a raw device address -- the kernels write there, None is returned in its place -- or None: the wrapper
-    allocates the array and returns it as an object with .ptr (its address, which feeds gather_rows / select_weights as it is) and
-    .read(stream) (numpy, waits).  src=SKIP (0): not wanted.  The capacity is D.nrows, else `cap`; the call then only enqueues on
-    `stream`.  With neither (cap=None), a count-only call comes first, the wrapper WAITS for it and sizes D to exactly count rows."""
+    -> (D, count, first, src): D holds the survivors in their order, `count` (one int32) says how many there are in all, first[v] is
+    the first row of class v (2^b int32), src[j] the row of P that D[j] came from (D.nrows int32; may be SKIP).  Only enqueues; count
+    first.  The arrays feed gather_rows / select_weights as they are."""
     L = _lib.lib()
     flags = _lib.LF1_KEEP_ZERO if keep_zero else 0
-    own_f = _IntScratch(1 << b) if first is None else None
-    own_c = _IntScratch(1) if count is None else None
-    fptr, cptr = own_f.ptr if own_f else first, own_c.ptr if own_c else count
+    fptr, own_f = _out(first, 1 << b)
+    cptr, own_c = _out(count, 1)
+
+    def call(Dm, sptr):
+        _lib.check(L.gf2_lf1_reduce_dev(Dm._on(stream), P._on(stream), c0, b, flags, fptr, cptr, sptr, stream), "gf2_lf1_reduce_dev")
+
     if D is None:
-        if cap is None:
-            if own_c is None:
-                raise ValueError("lf1_reduce: a raw count address needs D or cap (the wrapper cannot read the count to size D)")
-            none = DMat.wrap(None, 0, P.ncols, P.ld)
-            _lib.check(L.gf2_lf1_reduce_dev(none._on(stream), P._on(stream), c0, b, flags, fptr, cptr, None, stream), "gf2_lf1_reduce_dev")
-            cap = int(own_c.read(stream)[0])
+        if cap is None:   # an int32 count always fits a matrix
+            cap = _count_first("lf1_reduce", "rows", own_c, lambda: call(DMat.wrap(None, 0, P.ncols, P.ld), None), stream, fits=False)
         D = DMat(cap, P.ncols)
-    own_s = _IntScratch(D.nrows) if src is None and D.nrows > 0 else None
-    sptr = own_s.ptr if own_s else (src or None)
-    _lib.check(L.gf2_lf1_reduce_dev(D._on(stream), P._on(stream), c0, b, flags, fptr, cptr, sptr, stream), "gf2_lf1_reduce_dev")
-    for own in (own_f, own_c, own_s):
-        if own:
-            own.mat._streams.add(stream)
+    sptr, own_s = _out(src, D.nrows)
+    call(D, sptr)
+    _used(stream, own_f, own_c, own_s)
     return D, own_c, own_f, own_s
 
 
@@ -635,112 +684,69 @@ def lf2_plan(nrows, ncols, b):
     """How the class sort and an LF2 round over nrows x ncols with a window of b bits run (no device needed) -> (sort passes, key bits
     per pass, threads per workgroup, LDS bytes of the sort kernels, rows per sort tile, rows per run of the pair kernels, lanes per
     row of the pair scatter, scratch bytes of class_sort, scratch bytes of lf2_reduce); None for a bad shape."""
-    out = (ctypes.c_longlong * 8)()
-    v = _lib.lib().gf2_lf2_plan(nrows, ncols, b, out)
-    return None if v < 0 else (v,) + tuple(int(x) for x in out)
-
-
-class _Int64Scratch(_IntScratch):
-    """one device int64 (the count of lf2_reduce)"""
-
-    def __init__(self):
-        _IntScratch.__init__(self, 2)
-
-    def read(self, stream):
-        return _IntScratch.read(self, stream).view(np.int64)
+    return _plan(_lib.lib().gf2_lf2_plan, (nrows, ncols, b), 8)
 
 
 def class_sort(P, c0, b, order=None, skeys=None, stream=None):
     """The rows of P sorted by their bits [c0, c0 + b), ties in ascending row order (a stable sort; include/m4ri_hip_lf2.h)
-    -> (order, skeys): order[s] the row at sorted position s, skeys[s] its key.  Each is a raw device address of P.nrows int32 -- the
-    kernels write there, the call only enqueues on `stream` and None is returned in its place -- or None: the wrapper allocates the
-    array and returns it as an object with .ptr and .read(stream) (numpy, waits).  skeys=SKIP (0): not wanted."""
-    own_o = _IntScratch(max(P.nrows, 1)) if order is None else None   # an address even where no row is sorted
-    own_k = _IntScratch(max(P.nrows, 1)) if skeys is None else None
-    for own in (own_o, own_k):
-        if own:
-            own.count = P.nrows
-    kptr = own_k.ptr if own_k else (skeys or None)
-    _lib.check(_lib.lib().gf2_class_sort_dev(P._on(stream), c0, b, own_o.ptr if own_o else order, kptr, stream), "gf2_class_sort_dev")
-    for own in (own_o, own_k):
-        if own:
-            own.mat._streams.add(stream)
+    -> (order, skeys): order[s] the row at sorted position s, skeys[s] its key, P.nrows int32 each; skeys may be SKIP.  Only enqueues;
+    the objects are always there (an address even where no row is sorted)."""
+    optr, own_o = _out(order, P.nrows, always=True)
+    kptr, own_k = _out(skeys, P.nrows, always=True)
+    _lib.check(_lib.lib().gf2_class_sort_dev(P._on(stream), c0, b, optr, kptr, stream), "gf2_class_sort_dev")
+    _used(stream, own_o, own_k)
     return own_o, own_k
 
 
 def lf2_reduce(P, c0, b, D=None, cap=None, count=None, lo=None, hi=None, stream=None):
     """One LF2 round of a BKW reduction (include/m4ri_hip_lf2.h): the rows of P are partitioned by their bits [c0, c0 + b) and every
-    pair of rows inside a class is XORed.  -> (D, count, lo, hi), all on the device: D holds the pairs, classes by ascending key and
-    the pairs of a class by (higher row, lower row) (D.nrows is the capacity; `count`, an int64, says how many there are in all),
-    lo[j] < hi[j] the rows of P that D[j] came from.  Each of `count`, `lo` and `hi` is a raw device address -- the kernels write
-    there, None is returned in its place -- or None: the wrapper allocates the array and returns it as an object with .ptr (which
-    feeds gather_rows as it is) and .read(stream) (numpy, waits).  lo / hi = SKIP (0): not wanted.  The capacity is D.nrows, else
-    `cap`; the call then only enqueues on `stream`.  With neither (cap=None), a count-only call comes first, the wrapper WAITS for it
-    and sizes D to exactly count rows."""
+    pair of rows inside a class is XORed.  -> (D, count, lo, hi): D holds the pairs, classes by ascending key and the pairs of a class
+    by (higher row, lower row); `count` (one int64) says how many there are in all; lo[j] < hi[j] are the rows of P that D[j] came
+    from (D.nrows int32 each; may be SKIP; they feed gather_rows as they are).  Only enqueues; count first."""
     L = _lib.lib()
-    own_c = _Int64Scratch() if count is None else None
-    cptr = own_c.ptr if own_c else count
+    cptr, own_c = _out(count, 1, dtype=np.int64)
+
+    def call(Dm, lptr, hptr):
+        _lib.check(L.gf2_lf2_reduce_dev(Dm._on(stream), P._on(stream), c0, b, cptr, lptr, hptr, stream), "gf2_lf2_reduce_dev")
+
     if D is None:
         if cap is None:
-            if own_c is None:
-                raise ValueError("lf2_reduce: a raw count address needs D or cap (the wrapper cannot read the count to size D)")
-            none = DMat.wrap(None, 0, P.ncols, P.ld)
-            _lib.check(L.gf2_lf2_reduce_dev(none._on(stream), P._on(stream), c0, b, cptr, None, None, stream), "gf2_lf2_reduce_dev")
-            cap = int(own_c.read(stream)[0])
-            if cap >= 1 << 31:
-                raise ValueError("lf2_reduce: %d pairs do not fit a matrix; give D or cap" % cap)
+            cap = _count_first("lf2_reduce", "pairs", own_c, lambda: call(DMat.wrap(None, 0, P.ncols, P.ld), None, None), stream)
         D = DMat(cap, P.ncols)
-    own_l = _IntScratch(D.nrows) if lo is None and D.nrows > 0 else None
-    own_h = _IntScratch(D.nrows) if hi is None and D.nrows > 0 else None
-    lptr, hptr = own_l.ptr if own_l else (lo or None), own_h.ptr if own_h else (hi or None)
-    _lib.check(L.gf2_lf2_reduce_dev(D._on(stream), P._on(stream), c0, b, cptr, lptr, hptr, stream), "gf2_lf2_reduce_dev")
-    for own in (own_c, own_l, own_h):
-        if own:
-            own.mat._streams.add(stream)
-    return D, own_c, own_l, own_h
+    ptrs, owned = _outs((lo, hi), D.nrows)
+    call(D, *ptrs)
+    _used(stream, own_c, *owned)
+    return (D, own_c) + tuple(owned)
 
 
 def join_plan(nrows_a, nrows_b, ncols, b):
     """How the join of nrows_a x ncols with nrows_b x ncols on a window of b bits runs (no device needed) -> (passes of either sort,
     threads per workgroup, sorted positions of A per run R, lanes per row of the scatter, keys of B a workgroup stages in LDS at the
     most S, LDS bytes, scratch bytes, runs of A, the sorts' share of the scratch bytes); None for a bad shape."""
-    out = (ctypes.c_longlong * 8)()
-    v = _lib.lib().gf2_join_plan(nrows_a, nrows_b, ncols, b, out)
-    return None if v < 0 else (v,) + tuple(int(x) for x in out)
+    return _plan(_lib.lib().gf2_join_plan, (nrows_a, nrows_b, ncols, b), 8)
 
 
 def join(A, B, c0, b, D=None, cap=None, count=None, ia=None, ib=None, wt=None, wcols=None, stream=None):
     """The join of two pools on a window (include/m4ri_hip_join.h): every pair of a row of A and a row of B whose bits [c0, c0 + b)
-    are equal is XORed.  -> (D, count, ia, ib, wt), all on the device: D holds the pairs, classes by ascending key and the pairs of a
-    class by (row of A, row of B) (D.nrows is the capacity; `count`, an int64, says how many there are in all), ia[t] and ib[t] the
-    rows of A and B that D[t] came from, wt[t] the ones of D[t] in the columns wcols = (wc0, wc1) (None: all columns).  Each of
-    `count`, `ia`, `ib` and `wt` is a raw device address -- the kernels write there, None is returned in its place -- or None: the
-    wrapper allocates the array and returns it as an object with .ptr (which feeds gather_rows / select_weights as it is) and
-    .read(stream) (numpy, waits).  ia / ib / wt = SKIP (0): not wanted.  The capacity is D.nrows, else `cap`; the call then only
-    enqueues on `stream`.  With neither (cap=None), a count-only call comes first, the wrapper WAITS for it and sizes D to exactly
-    count rows.  A may be B: all ordered pairs of a class, (i, i) included."""
+    are equal is XORed.  -> (D, count, ia, ib, wt): D holds the pairs, classes by ascending key and the pairs of a class by (row of A,
+    row of B); `count` (one int64) says how many there are in all; ia[t] and ib[t] are the rows of A and B that D[t] came from, wt[t]
+    the ones of D[t] in the columns wcols = (wc0, wc1) (None: all columns) (D.nrows int32 each; may be SKIP; they feed gather_rows /
+    select_weights as they are).  Only enqueues; count first.  A may be B: all ordered pairs of a class, (i, i) included."""
     L = _lib.lib()
-    wc0, wc1 = (0, A.ncols) if wcols is None else wcols
-    own_c = _Int64Scratch() if count is None else None
-    cptr = own_c.ptr if own_c else count
+    wc0, wc1 = _wcols(A.ncols, wcols)
+    cptr, own_c = _out(count, 1, dtype=np.int64)
+
+    def call(Dm, pa, pb, pw):
+        rc = L.gf2_join_dev(Dm._on(stream), A._on(stream), B._on(stream), c0, b, cptr, pa, pb, pw, wc0, wc1, stream)
+        _lib.check(rc, "gf2_join_dev")
+
     if D is None:
         if cap is None:
-            if own_c is None:
-                raise ValueError("join: a raw count address needs D or cap (the wrapper cannot read the count to size D)")
-            none = DMat.wrap(None, 0, A.ncols, A.ld)
-            rc = L.gf2_join_dev(none._on(stream), A._on(stream), B._on(stream), c0, b, cptr, None, None, None, wc0, wc1, stream)
-            _lib.check(rc, "gf2_join_dev")
-            cap = int(own_c.read(stream)[0])
-            if cap >= 1 << 31:
-                raise ValueError("join: %d pairs do not fit a matrix; give D or cap" % cap)
+            cap = _count_first("join", "pairs", own_c, lambda: call(DMat.wrap(None, 0, A.ncols, A.ld), None, None, None), stream)
         D = DMat(cap, A.ncols)
-    owned = [_IntScratch(D.nrows) if given is None and D.nrows > 0 else None for given in (ia, ib, wt)]
-    ptrs = [own.ptr if own else (given or None) for own, given in zip(owned, (ia, ib, wt))]
-    rc = L.gf2_join_dev(D._on(stream), A._on(stream), B._on(stream), c0, b, cptr, ptrs[0], ptrs[1], ptrs[2], wc0, wc1, stream)
-    _lib.check(rc, "gf2_join_dev")
-    for own in [own_c] + owned:
-        if own:
-            own.mat._streams.add(stream)
+    ptrs, owned = _outs((ia, ib, wt), D.nrows)
+    call(D, *ptrs)
+    _used(stream, own_c, *owned)
     return (D, own_c) + tuple(owned)
 
 
@@ -749,26 +755,19 @@ def join_select_plan(nrows_a, nrows_b, ncols, b, wcols=None):
     workgroup, sorted positions of A per run R, lanes per pair of the weigh pass (by the words of the weight range wcols), lanes per
     row of the row store (by the row width), LDS bytes, scratch bytes, runs of A, outputs per round of the scatter G); None for a bad
     shape or range."""
-    wc0, wc1 = (0, ncols) if wcols is None else wcols
-    out = (ctypes.c_longlong * 8)()
-    v = _lib.lib().gf2_join_select_plan(nrows_a, nrows_b, ncols, b, wc0, wc1, out)
-    return None if v < 0 else (v,) + tuple(int(x) for x in out)
+    return _plan(_lib.lib().gf2_join_select_plan, (nrows_a, nrows_b, ncols, b) + tuple(_wcols(ncols, wcols)), 8)
 
 
 def join_select(A, B, c0, b, wcols, wlo, whi, D=None, cap=None, store=True, count=None, hits=None, ia=None, ib=None, wt=None, stream=None):
     """The weight-filtered join (include/m4ri_hip_join_select.h): of the pairs of join(A, B, c0, b), in its order, only the HITS -- those
     whose XOR has between wlo and whi ones in the columns wcols = (wc0, wc1) (None: all columns) -- are written.  -> (D, count, hits,
-    ia, ib, wt), all on the device: D[h], ia[h], ib[h], wt[h] for the h-th hit; `count`, an int64, the number of all pairs and `hits`,
-    an int64, the number of all hits, which may exceed the capacity.  The arrays follow join(): a raw device address (None is
-    returned in its place), None (the wrapper allocates the array and returns an object with .ptr and .read(stream)), and for ia / ib
-    / wt SKIP (0): not wanted.  The capacity is D.nrows, else `cap`; the call then only enqueues on `stream`.  With neither, a
-    counts-only call comes first, the wrapper WAITS for it and sizes D to exactly `hits` rows.  store=False: the rows are not stored
-    -- D is passed without data, None is returned in its place and only ia, ib and wt are written (the index-only mode)."""
+    ia, ib, wt): D[h], ia[h], ib[h], wt[h] for the h-th hit (D.nrows int32 each; may be SKIP); `count` (one int64) the number of all
+    pairs and `hits` (one int64) the number of all hits, which may exceed the capacity.  Only enqueues; count first, by `hits`;
+    store=False."""
     L = _lib.lib()
-    wc0, wc1 = (0, A.ncols) if wcols is None else wcols
-    own_c = _Int64Scratch() if count is None else None
-    own_h = _Int64Scratch() if hits is None else None
-    cptr, hptr = own_c.ptr if own_c else count, own_h.ptr if own_h else hits
+    wc0, wc1 = _wcols(A.ncols, wcols)
+    cptr, own_c = _out(count, 1, dtype=np.int64)
+    hptr, own_h = _out(hits, 1, dtype=np.int64)
 
     def call(Dm, pa, pb, pw):
         rc = L.gf2_join_select_dev(Dm._on(stream), A._on(stream), B._on(stream), c0, b, wc0, wc1, wlo, whi, cptr, hptr, pa, pb, pw, stream)
@@ -778,19 +777,11 @@ def join_select(A, B, c0, b, wcols, wlo, whi, D=None, cap=None, store=True, coun
         raise ValueError("join_select: store=False takes no D")
     if D is None:
         if cap is None:
-            if own_h is None:
-                raise ValueError("join_select: a raw hits address needs D or cap (the wrapper cannot read the hits to size D)")
-            call(DMat.wrap(None, 0, A.ncols, A.ld), None, None, None)
-            cap = int(own_h.read(stream)[0])
-            if cap >= 1 << 31:
-                raise ValueError("join_select: %d hits do not fit a matrix; give D or cap" % cap)
-        D = DMat(cap, A.ncols) if store else DMat.wrap(None, cap, A.ncols, max((A.ncols + 63) // 64, 1))
-    owned = [_IntScratch(D.nrows) if given is None and D.nrows > 0 else None for given in (ia, ib, wt)]
-    ptrs = [own.ptr if own else (given or None) for own, given in zip(owned, (ia, ib, wt))]
+            cap = _count_first("join_select", "hits", own_h, lambda: call(DMat.wrap(None, 0, A.ncols, A.ld), None, None, None), stream)
+        D = DMat(cap, A.ncols) if store else _unstored(cap, A.ncols)
+    ptrs, owned = _outs((ia, ib, wt), D.nrows)
     call(D, *ptrs)
-    for own in [own_c, own_h] + owned:
-        if own:
-            own.mat._streams.add(stream)
+    _used(stream, own_c, own_h, *owned)
     return (D if store else None, own_c, own_h) + tuple(owned)
 
 
@@ -803,26 +794,18 @@ def near_plan(nrows_a, nrows_b, ncols, wcols=None):
     it keeps in registers per row of A, 1, 2, 4, 8 or 16, and 0 for the wide kernel; threads per workgroup; rows of A per workgroup;
     the chunks S that B is cut into; rows of B per chunk; LDS bytes; scratch bytes; the words of a row that hold a column of the
     range); None for a bad shape or range."""
-    wc0, wc1 = (0, ncols) if wcols is None else wcols
-    out = (ctypes.c_longlong * 8)()
-    v = _lib.lib().gf2_near_plan(nrows_a, nrows_b, ncols, wc0, wc1, out)
-    return None if v < 0 else tuple(int(x) for x in out)
+    return _plan(_lib.lib().gf2_near_plan, (nrows_a, nrows_b, ncols) + tuple(_wcols(ncols, wcols)), 8, lead=False)
 
 
 def near_pairs(A, B, wcols, wlo, whi, flags=0, D=None, cap=None, store=True, hits=None, ia=None, ib=None, wt=None, stream=None):
     """The pairs of a row of A and a row of B that are close (include/m4ri_hip_near.h): of all pairs (ia, ib) that `flags` admits
     (NEAR_OFF_DIAGONAL: not ia == ib; NEAR_UPPER: only ia < ib), ordered by (ia, ib), only the HITS -- those whose XOR has between wlo
-    and whi ones in the columns wcols = (wc0, wc1) (None: all columns) -- are written.  -> (D, hits, ia, ib, wt), all on the device:
-    D[h], ia[h], ib[h], wt[h] for the h-th hit and `hits`, an int64, the number of all hits, which may exceed the capacity.  The
-    arrays follow join_select(): a raw device address (None is returned in its place), None (the wrapper allocates the array and
-    returns an object with .ptr and .read(stream)), and for ia / ib / wt SKIP (0): not wanted.  The capacity is D.nrows, else `cap`;
-    the call then only enqueues on `stream`.  With neither, a counts-only call comes first, the wrapper WAITS for it and sizes D to
-    exactly `hits` rows.  store=False: the rows are not stored -- D is passed without data, None is returned in its place and only
-    ia, ib and wt are written (the index-only mode).  A may be B."""
+    and whi ones in the columns wcols = (wc0, wc1) (None: all columns) -- are written.  -> (D, hits, ia, ib, wt): D[h], ia[h], ib[h],
+    wt[h] for the h-th hit (D.nrows int32 each; may be SKIP) and `hits` (one int64), the number of all hits, which may exceed the
+    capacity.  Only enqueues; count first, by `hits`; store=False.  A may be B."""
     L = _lib.lib()
-    wc0, wc1 = (0, A.ncols) if wcols is None else wcols
-    own_h = _Int64Scratch() if hits is None else None
-    hptr = own_h.ptr if own_h else hits
+    wc0, wc1 = _wcols(A.ncols, wcols)
+    hptr, own_h = _out(hits, 1, dtype=np.int64)
 
     def call(Dm, pa, pb, pw):
         rc = L.gf2_near_pairs_dev(Dm._on(stream), A._on(stream), B._on(stream), wc0, wc1, wlo, whi, flags, hptr, pa, pb, pw, stream)
@@ -832,38 +815,23 @@ def near_pairs(A, B, wcols, wlo, whi, flags=0, D=None, cap=None, store=True, hit
         raise ValueError("near_pairs: store=False takes no D")
     if D is None:
         if cap is None:
-            if own_h is None:
-                raise ValueError("near_pairs: a raw hits address needs D or cap (the wrapper cannot read the hits to size D)")
-            call(DMat.wrap(None, 0, A.ncols, A.ld), None, None, None)
-            cap = int(own_h.read(stream)[0])
-            if cap >= 1 << 31:
-                raise ValueError("near_pairs: %d hits do not fit a matrix; give D or cap" % cap)
-        D = DMat(cap, A.ncols) if store else DMat.wrap(None, cap, A.ncols, max((A.ncols + 63) // 64, 1))
-    owned = [_IntScratch(D.nrows) if given is None and D.nrows > 0 else None for given in (ia, ib, wt)]
-    ptrs = [own.ptr if own else (given or None) for own, given in zip(owned, (ia, ib, wt))]
+            cap = _count_first("near_pairs", "hits", own_h, lambda: call(DMat.wrap(None, 0, A.ncols, A.ld), None, None, None), stream)
+        D = DMat(cap, A.ncols) if store else _unstored(cap, A.ncols)
+    ptrs, owned = _outs((ia, ib, wt), D.nrows)
     call(D, *ptrs)
-    for own in [own_h] + owned:
-        if own:
-            own.mat._streams.add(stream)
+    _used(stream, own_h, *owned)
     return (D if store else None, own_h) + tuple(owned)
 
 
 def nearest(A, B, wcols=None, flags=0, idx=None, dist=None, stream=None):
     """For every row of A the nearest row of B on the columns wcols = (wc0, wc1) (None: all columns) among those that `flags` admits
-    (include/m4ri_hip_near.h) -> (idx, dist): idx[i] the lowest such row, dist[i] its distance, both -1 where no row is admitted.
-    Each is a raw device address of A.nrows int32 (None is returned in its place), None (the wrapper allocates the array and returns
-    an object with .ptr and .read(stream)) or SKIP (0): not wanted (not both).  The call only enqueues on `stream`."""
-    wc0, wc1 = (0, A.ncols) if wcols is None else wcols
-    owned = [_IntScratch(max(A.nrows, 1)) if given is None else None for given in (idx, dist)]
-    for own in owned:
-        if own:
-            own.count = A.nrows
-    ptrs = [own.ptr if own else (given or None) for own, given in zip(owned, (idx, dist))]
+    (include/m4ri_hip_near.h) -> (idx, dist): idx[i] the lowest such row, dist[i] its distance, both -1 where no row is admitted;
+    A.nrows int32 each; either may be SKIP, not both.  Only enqueues; the objects are always there."""
+    wc0, wc1 = _wcols(A.ncols, wcols)
+    ptrs, owned = _outs((idx, dist), A.nrows, always=True)
     rc = _lib.lib().gf2_nearest_dev(A._on(stream), B._on(stream), wc0, wc1, flags, ptrs[0], ptrs[1], stream)
     _lib.check(rc, "gf2_nearest_dev")
-    for own in owned:
-        if own:
-            own.mat._streams.add(stream)
+    _used(stream, *owned)
     return tuple(owned)
 
 
@@ -878,32 +846,17 @@ def subset_sums_plan(n, ncols, p, count):
     """How `count` sums of p of n rows of ncols columns run (include/m4ri_hip_sums.h, no device needed) -> (kernel id: 0 .. 3 S in LDS
     with 1, 2, 8, 64 lanes per row, 4 .. 7 S from global memory likewise; threads per workgroup; ranks per workgroup R; lanes per row;
     LDS bytes; workgroups; scratch bytes); None for a bad shape."""
-    out = (ctypes.c_longlong * 6)()
-    v = _lib.lib().gf2_subset_sums_plan(n, ncols, p, count, out)
-    return None if v < 0 else (v,) + tuple(int(x) for x in out)
-
-
-class _TupleScratch(_IntScratch):
-    """count tuples of p device ints (the idx of subset_sums / unrank_subsets); read() gives shape (count, p)"""
-
-    def __init__(self, count, p):
-        _IntScratch.__init__(self, count * p)
-        self.p = p
-
-    def read(self, stream):
-        return _IntScratch.read(self, stream).reshape(-1, self.p)
+    return _plan(_lib.lib().gf2_subset_sums_plan, (n, ncols, p, count), 6)
 
 
 def subset_sums(S, p, base=None, rank0=0, count=None, D=None, idx=None, wt=None, wcols=None, store=True, stream=None):
     """All XORs of p rows of S in rank order (include/m4ri_hip_sums.h): D[t] = base ^ S[c_1] ^ ... ^ S[c_p] for the subset c_1 < ... <
-    c_p of rank rank0 + t in the colexicographic order, rank = C(c_1, 1) + ... + C(c_p, p).  -> (D, idx, wt), all on the device:
-    idx[t] = (c_1 .. c_p), wt[t] the ones of D[t] in the columns wcols = (wc0, wc1) (None: all columns).  base: None or a 1-row DMat
-    (the syndrome).  The window is D.nrows rows, else `count`, else (count=None) everything from rank0 up to C(n, p); ValueError when
-    that does not fit a matrix (2^31 - 1 rows).  store=False: the rows are not stored -- no D is allocated, None is returned in its
-    place and only idx and wt are written (the weights of all candidates of Lee-Brickell).  Each of `idx` and `wt` is a raw device
-    address -- the kernel writes there, None is returned in its place -- or None: the wrapper allocates the array and returns it as
-    an object with .ptr (wt feeds select_weights, idx gather_rows as they are) and .read(stream) (numpy, waits; idx: shape
-    (count, p)); SKIP (0): not wanted.  The call only enqueues on `stream`."""
+    c_p of rank rank0 + t in the colexicographic order, rank = C(c_1, 1) + ... + C(c_p, p).  -> (D, idx, wt): idx[t] = (c_1 .. c_p)
+    (count * p int32; read(): shape (count, p); feeds gather_rows), wt[t] the ones of D[t] in the columns wcols = (wc0, wc1) (None: all
+    columns) (count int32; feeds select_weights); either may be SKIP.  base: None or a 1-row DMat (the syndrome).  The window is
+    D.nrows rows, else `count`, else (count=None) everything from rank0 up to C(n, p); ValueError when that does not fit a matrix
+    (2^31 - 1 rows): there is no count-only call.  store=False: only idx and wt are written (the weights of all candidates of
+    Lee-Brickell).  Only enqueues."""
     total = subset_count(S.nrows, p)
     if total is None:
         raise ValueError("subset_sums: p = %d is outside 1 .. 4, or C(%d, %d) passes 2^62" % (p, S.nrows, p))
@@ -918,40 +871,30 @@ def subset_sums(S, p, base=None, rank0=0, count=None, D=None, idx=None, wt=None,
     if count >= 1 << 31:
         raise ValueError("subset_sums: %d sums do not fit a matrix; give count, D or rank0" % count)
     if D is None:
-        D = DMat(count, S.ncols) if store else DMat.wrap(None, count, S.ncols, max((S.ncols + 63) // 64, 1))
-    wc0, wc1 = (0, S.ncols) if wcols is None else wcols
-    own_i = _TupleScratch(count, p) if idx is None and count > 0 else None
-    own_w = _IntScratch(count) if wt is None and count > 0 else None
-    iptr, wptr = own_i.ptr if own_i else (idx or None), own_w.ptr if own_w else (wt or None)
+        D = DMat(count, S.ncols) if store else _unstored(count, S.ncols)
+    wc0, wc1 = _wcols(S.ncols, wcols)
+    iptr, own_i = _out(idx, count, width=p)
+    wptr, own_w = _out(wt, count)
     rc = _lib.lib().gf2_subset_sums_dev(D._on(stream), S._on(stream), base._on(stream) if base is not None else None, p, rank0, iptr, wptr,
                                         wc0, wc1, stream)
     _lib.check(rc, "gf2_subset_sums_dev")
-    for own in (own_i, own_w):
-        if own:
-            own.mat._streams.add(stream)
+    _used(stream, own_i, own_w)
     return (D if store else None), own_i, own_w
 
 
 def unrank_subsets(ranks, count, p, n, rank0=0, idx=None, bad=None, stream=None):
     """The subsets of the ranks rank0 + ranks[t], t < count, of the order of subset_sums over n rows -> (idx, bad): idx[t] = (c_1 ..
-    c_p); a rank of -1 (what select_weights leaves behind its count) gives p times -1, any other rank outside [0, C(n, p)) as well
-    and is reported in `bad`.  `ranks` is a raw device address of count int32 (what select_weights wrote, or the ia / ib of a join
-    gathered at the hits) or a list / numpy int array that the wrapper uploads.  `idx` is a raw device address of count * p int32 --
-    None is returned in its place -- or None: the wrapper allocates the array and returns it as an object with .ptr and
-    .read(stream) (numpy of shape (count, p), waits).  `bad` follows gather_rows(): a raw device address of an int the caller has
-    zeroed, or SKIP (0) -- the call then only enqueues on `stream` and None is returned in its place -- or None: the wrapper
-    allocates a zeroed int, WAITS for `stream` and returns a bool."""
+    c_p) (count * p int32; read(): shape (count, p)); a rank of -1 (what select_weights leaves behind its count) gives p times -1, any
+    other rank outside [0, C(n, p)) as well and is reported in `bad`.  `ranks`: count int32, an input array (what select_weights wrote,
+    or the ia / ib of a join gathered at the hits).  `bad` as in gather_rows(), but None is the default: only enqueues when `bad` is an
+    address or SKIP."""
     rptr, keep = _device_ints(ranks, count, "unrank_subsets", stream)
-    own_i = _TupleScratch(count, p) if idx is None and count > 0 else None
-    own_b = None
-    if bad is None:
-        own_b = _IntUpload([0], stream)
-        bad = own_b.ptr
-    rc = _lib.lib().gf2_unrank_subsets_dev(rptr, count, rank0, p, n, own_i.ptr if own_i else (idx or None), bad or None, stream)
+    iptr, own_i = _out(idx, count, width=p)
+    bptr, own_b = _bad_int(bad, stream)
+    rc = _lib.lib().gf2_unrank_subsets_dev(rptr, count, rank0, p, n, iptr, bptr, stream)
     _lib.check(rc, "gf2_unrank_subsets_dev")
-    if own_i:
-        own_i.mat._streams.add(stream)
-    return own_i, (bool(own_b.read(stream)[0]) if own_b else None)
+    _used(stream, own_i)
+    return own_i, _bad_result(own_b, stream)
 
 
 def draw_plan(what, count_or_k=0, n=1, thr=0):
@@ -961,9 +904,7 @@ def draw_plan(what, count_or_k=0, n=1, thr=0):
     bytes, sort passes, key bits, 0); None for a bad shape."""
     code = {"bernoulli": _lib.DRAW_BERNOULLI, "indices": _lib.DRAW_INDICES, "subsets": _lib.DRAW_SUBSETS,
             "permutation": _lib.DRAW_PERMUTATION}.get(what, what)
-    out = (ctypes.c_longlong * 4)()
-    rc = _lib.lib().gf2_draw_plan(code, count_or_k, n, thr, out)
-    return None if rc < 0 else tuple(int(x) for x in out)
+    return _plan(_lib.lib().gf2_draw_plan, (code, count_or_k, n, thr), 4, lead=False)
 
 
 def bernoulli(D, thr, seed, accumulate=False, row0=0, col_word0=0, full_ncols=0, stream=None):
@@ -979,39 +920,22 @@ def bernoulli(D, thr, seed, accumulate=False, row0=0, col_word0=0, full_ncols=0,
     return D
 
 
-def _draw_ints(name, call, count, out, stream):
-    """the int output of a draw: `out` is a raw device address (the call only enqueues, None is returned) or None: the wrapper
-    allocates the array and returns it as an object with .ptr and .read(stream)"""
-    own = None
-    if out is None:
-        own = _IntScratch(max(count, 1))   # an address even where nothing is drawn
-        own.count = count
-    _lib.check(call(own.ptr if own else out), name)
-    if own:
-        own.mat._streams.add(stream)
-    return own
-
-
 def draw_indices(count, n, seed, out=None, stream=None):
-    """`count` independent draws from [0, n) (include/m4ri_hip_draw.h); they feed gather_rows as the device array they are.  `out` is
-    a raw device address of count int32 -- the call only enqueues on `stream`, None is returned -- or None: the wrapper allocates the
-    array and returns it as an object with .ptr and .read(stream) (numpy, waits)."""
+    """`count` independent draws from [0, n) (include/m4ri_hip_draw.h): `out`, count int32; they feed gather_rows as the device array
+    they are.  Only enqueues; the object is always there (an address even where nothing is drawn)."""
     L = _lib.lib()
-    return _draw_ints("gf2_draw_indices_dev", lambda p: L.gf2_draw_indices_dev(p, count, n, seed, stream), count, out, stream)
+    return _one_array("gf2_draw_indices_dev", lambda p: L.gf2_draw_indices_dev(p, count, n, seed, stream), out, count, stream, False, always=True)
 
 
 def draw_subsets(batch, k, n, seed, max_rounds=0, out=None, unfinished=None, stream=None):
     """`batch` ordered k-tuples of distinct values from [0, n), one per guess of a pooled-Gauss round (include/m4ri_hip_draw.h)
-    -> (sub, unfinished).  Each is a raw device address (batch * k int32; one int32) -- None is returned in its place -- or None: the
-    wrapper allocates it and returns an object with .ptr and .read(stream).  unfinished=SKIP (0): not wanted.  A position that has not
-    settled after max_rounds rounds (0: 64) reads -1.  The call only enqueues on `stream`."""
+    -> (sub, unfinished): `out` batch * k int32 (the object is always there), `unfinished` one int32, may be SKIP.  A position that has
+    not settled after max_rounds rounds (0: 64) reads -1.  Only enqueues."""
     L = _lib.lib()
-    own_u = _IntScratch(1) if unfinished is None else None
-    uptr = own_u.ptr if own_u else (unfinished or None)
-    own_s = _draw_ints("gf2_draw_subsets_dev", lambda p: L.gf2_draw_subsets_dev(p, batch, k, n, seed, max_rounds, uptr, stream),
-                       batch * k, out, stream)
-    if own_u:
-        own_u.mat._streams.add(stream)
+    uptr, own_u = _out(unfinished, 1)
+    own_s = _one_array("gf2_draw_subsets_dev", lambda p: L.gf2_draw_subsets_dev(p, batch, k, n, seed, max_rounds, uptr, stream), out, batch * k,
+                       stream, False, always=True)
+    _used(stream, own_u)
     return own_s, own_u
 
 
@@ -1019,7 +943,7 @@ def draw_permutation(n, seed, out=None, stream=None):
     """A permutation of 0 .. n - 1: the stable argsort of 30-bit Philox keys (include/m4ri_hip_draw.h); it feeds gather_cols and
     gather_rows as the device array it is.  `out` as in draw_indices()."""
     L = _lib.lib()
-    return _draw_ints("gf2_draw_permutation_dev", lambda p: L.gf2_draw_permutation_dev(p, n, seed, stream), n, out, stream)
+    return _one_array("gf2_draw_permutation_dev", lambda p: L.gf2_draw_permutation_dev(p, n, seed, stream), out, n, stream, False, always=True)
 
 
 def lpn_samples(N, k, secret, thr, seed, stream=None):
@@ -1138,7 +1062,7 @@ class CoverCode:
         if not self.has_table:
             return None
         if self._dev is None:
-            self._dev = _IntUpload((self.leaders() if self._table is None else self._table).view(np.int32))
+            self._dev = _Ints(values=(self.leaders() if self._table is None else self._table).view(np.int32))
         return self._dev.ptr
 
 
@@ -1167,30 +1091,22 @@ def cover_plan(nrows, p_ncols, segments):
         codes, arr, seg = _cover_args(segments)
     except ValueError:
         return None
-    out = (ctypes.c_longlong * 8)()
-    v = _lib.lib().gf2_cover_plan(nrows, p_ncols, arr, len(codes), seg, len(segments), out)
-    return None if v < 0 else (v,) + tuple(int(x) for x in out)
+    return _plan(_lib.lib().gf2_cover_plan, (nrows, p_ncols, arr, len(codes), seg, len(segments)), 8)
 
 
 def cover_reduce(P, c0, segments, D=None, dist=None, stream=None):
     """The covering-code reduction (include/m4ri_hip_cover.h): the columns of P from c0 on are cut into blocks, block j as long as
     segments[j] (a CoverCode), every block is decoded to the nearest codeword and replaced by its message -> (D, dist): D (default: a
     new P.nrows x K matrix, K = the sum of the codes' k) holds the messages side by side, dist[i] the number of bits of row i that the
-    decoding flipped or dropped.  `dist` is a raw device address of P.nrows int32 -- the kernel writes there, None is returned in its
-    place -- or SKIP (0): not wanted, or None: the wrapper allocates the array and returns it as an object with .ptr and .read(stream)
-    (numpy, waits).  The call only enqueues on `stream`, except that a code's table is uploaded (and waited for) the first time the code
-    is used: table_ptr() does that ahead of a chain."""
+    decoding flipped or dropped (P.nrows int32; may be SKIP).  Only enqueues, except that a code's table is uploaded (and waited for)
+    the first time the code is used: table_ptr() does that ahead of a chain."""
     codes, arr, seg = _cover_args(segments)
     tables = (ctypes.c_void_p * max(len(codes), 1))(*[code.table_ptr() for code in codes])
     if D is None:
         D = DMat(P.nrows, sum(code.k for code in segments))
-    own = _IntScratch(P.nrows) if dist is None and P.nrows > 0 else None
-    dptr = own.ptr if own else (dist or None)
-    rc = _lib.lib().gf2_cover_reduce_dev(D._on(stream), P._on(stream), c0, arr, len(codes), seg, len(segments), tables, dptr, stream)
-    _lib.check(rc, "gf2_cover_reduce_dev")
-    if own:
-        own.mat._streams.add(stream)
-    return D, own
+    L = _lib.lib()
+    return D, _one_array("gf2_cover_reduce_dev", lambda p: L.gf2_cover_reduce_dev(D._on(stream), P._on(stream), c0, arr, len(codes), seg,
+                                                                                   len(segments), tables, p, stream), dist, P.nrows, stream, False)
 
 
 def nullspace(A, stream=None):
