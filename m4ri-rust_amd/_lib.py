@@ -298,6 +298,14 @@ _TABLES["m4ri_hip_near.h"] = {
 }
 NEAR_SYMBOLS = tuple(_TABLES["m4ri_hip_near.h"])
 
+# ... and include/m4ri_hip_unique.h (tests/test_unique_contract.py)
+_TABLES["m4ri_hip_unique.h"] = {
+    "gf2_sort_rows_dev": (_I, [DMatP, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_unique_rows_dev": (_I, [DMatP, _I, _I, ctypes.c_void_p, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_sort_rows_plan": (_I, [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
+}
+UNIQUE_SYMBOLS = tuple(_TABLES["m4ri_hip_unique.h"])
+
 _lib = None
 
 

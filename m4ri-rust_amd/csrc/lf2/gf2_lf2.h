@@ -1,5 +1,5 @@
 // gf2_lf2.h -- launchers of gf2_lf2.hip and the enqueue of the whole class sort (lf2_host.cpp; callers: lf2_host.cpp, join_host.cpp,
-// draw_host.cpp).  Arguments are checked by the callers.  Everything here only enqueues on `stream`.  key(i) = bits [c0, c0 + b) of row i of P.
+// draw_host.cpp, unique_host.cpp).  Arguments are checked by the callers.  Everything here only enqueues on `stream`.  key(i) = bits [c0, c0 + b) of row i of P.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

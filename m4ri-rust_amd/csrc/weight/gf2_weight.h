@@ -1,4 +1,4 @@
-// gf2_weight.h -- launchers of gf2_weight.hip (callers: weight_host.cpp).  Arguments are checked by the callers; an empty A launches
+// gf2_weight.h -- launchers of gf2_weight.hip (callers: weight_host.cpp; gf2k_weight_select also unique/unique_host.cpp).  Arguments are checked by the callers; an empty A launches
 // nothing (the callers clear the output).  Every launcher only enqueues on `stream`.
 #pragma once
 #include <hip/hip_runtime.h>

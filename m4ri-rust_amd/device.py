@@ -230,6 +230,19 @@ class DMat:
         idx, dist = nearest(self, other, wcols, flags=flags)
         return idx.read(None), dist.read(None)
 
+    def sort_rows(self, c0=0, c1=None):
+        """The rows of self sorted by their columns [c0, c1) (None: to the last column), ties in ascending row order, as the device
+        array of the row at every sorted position (.ptr feeds gather_rows, .read(stream) gives numpy; include/m4ri_hip_unique.h)."""
+        return sort_rows(self, c0, c1, head=SKIP)[0]
+
+    def unique_rows(self, c0=0, c1=None):
+        """The rows of self without those that repeat an earlier row on the columns [c0, c1) (None: to the last column), in the order
+        they had, as a new DMat (include/m4ri_hip_unique.h).  The count of the kept rows is read back once, to size the result."""
+        keep, count, _ = unique_rows(self, c0, c1, cap=self.nrows, rep=SKIP)
+        n = int(count.read(None)[0])
+        D = DMat(n, self.ncols)
+        return gather_rows(self, keep.ptr, D=D)[0] if n else D
+
     def subset_sums(self, p, base=None):
         """All C(nrows, p) XORs of p rows of self (each ^ base, a 1-row DMat, if given) as a new DMat, in the colexicographic order of
         the subsets: row C(c_1, 1) + ... + C(c_p, p) is the sum of the rows c_1 < ... < c_p (include/m4ri_hip_sums.h)."""
@@ -833,6 +846,57 @@ def nearest(A, B, wcols=None, flags=0, idx=None, dist=None, stream=None):
     _lib.check(rc, "gf2_nearest_dev")
     _used(stream, *owned)
     return tuple(owned)
+
+
+def _crange(ncols, c0, c1):
+    return c0, ncols if c1 is None else c1
+
+
+def sort_rows_plan(nrows, ncols, c0=0, c1=None):
+    """How the row sort on the columns [c0, c1) (c1 = None: to the last column) and the duplicate removal run
+    (include/m4ri_hip_unique.h, no device needed) -> (radix passes, windows, bits per window, radix passes, launches of sort_rows
+    without head, launches of unique_rows, scratch bytes of sort_rows, scratch bytes of unique_rows, rows per run of the head kernels);
+    None for a bad shape or range."""
+    return _plan(_lib.lib().gf2_sort_rows_plan, (nrows, ncols) + _crange(ncols, c0, c1), 8)
+
+
+def sort_rows(P, c0=0, c1=None, order=None, head=None, stream=None):
+    """The rows of P sorted by their columns [c0, c1) (c1 = None: to the last column; column c1 - 1 is the most significant bit), ties
+    in ascending row order (a stable sort on a range of any width; include/m4ri_hip_unique.h) -> (order, head): order[s] the row at
+    sorted position s, head[s] the first sorted position of the class of s, P.nrows int32 each; head may be SKIP.  Only enqueues; the
+    objects are always there (an address even where no row is sorted).  gather_rows by `order` gives the canonical form of a list."""
+    c0, c1 = _crange(P.ncols, c0, c1)
+    ptrs, owned = _outs((order, head), P.nrows, always=True)
+    _lib.check(_lib.lib().gf2_sort_rows_dev(P._on(stream), c0, c1, ptrs[0], ptrs[1], stream), "gf2_sort_rows_dev")
+    _used(stream, *owned)
+    return tuple(owned)
+
+
+def unique_rows(P, c0=0, c1=None, keep=None, cap=None, count=None, rep=None, stream=None):
+    """The first occurrence of every distinct value of the columns [c0, c1) of P's rows (c1 = None: to the last column;
+    include/m4ri_hip_unique.h) -> (keep, count, rep): keep holds the kept rows, ascending (`cap` int32; it feeds gather_rows as it is);
+    `count` (one int32) says how many there are in all, which may exceed cap; rep[i] is the lowest row equal to row i on the range
+    (P.nrows int32; may be SKIP).  Only enqueues; count first, by `count`: with neither keep nor cap a count-only call (keep=SKIP,
+    cap=0) comes first, the wrapper WAITS for it and sizes keep to exactly that many -- the rows are sorted twice; cap=P.nrows always
+    suffices and sorts once.  A raw keep address needs cap."""
+    L = _lib.lib()
+    c0, c1 = _crange(P.ncols, c0, c1)
+    cptr, own_c = _out(count, 1)
+
+    def call(kptr, capacity, rptr):
+        _lib.check(L.gf2_unique_rows_dev(P._on(stream), c0, c1, kptr, capacity, cptr, rptr, stream), "gf2_unique_rows_dev")
+
+    if keep is not None and keep == SKIP:
+        cap = 0
+    if cap is None:
+        if keep is not None:
+            raise ValueError("unique_rows: a raw keep address needs cap (the number of int32 it holds)")
+        cap = _count_first("unique_rows", "rows", own_c, lambda: call(None, 0, None), stream, fits=False)
+    kptr, own_k = _out(keep, cap)
+    rptr, own_r = _out(rep, P.nrows)
+    call(kptr, cap, rptr)
+    _used(stream, own_k, own_c, own_r)
+    return own_k, own_c, own_r
 
 
 def subset_count(n, p):
