@@ -306,6 +306,13 @@ _TABLES["m4ri_hip_unique.h"] = {
 }
 UNIQUE_SYMBOLS = tuple(_TABLES["m4ri_hip_unique.h"])
 
+# ... and include/m4ri_hip_find.h (tests/test_find_contract.py)
+_TABLES["m4ri_hip_find.h"] = {
+    "gf2_find_rows_dev": (_I, [DMatP, DMatP, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_find_rows_plan": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
+}
+FIND_SYMBOLS = tuple(_TABLES["m4ri_hip_find.h"])
+
 _lib = None
 
 

@@ -243,6 +243,30 @@ class DMat:
         D = DMat(n, self.ncols)
         return gather_rows(self, keep.ptr, D=D)[0] if n else D
 
+    def find_in(self, B, c0=0, c1=None):
+        """For every row of self the lowest row of B that equals it on the columns [c0, c1) (None: to the last column of the narrower
+        of the two), -1 where there is none, as a device array (.ptr feeds gather_rows, .read(stream) gives numpy;
+        include/m4ri_hip_find.h)."""
+        return find_rows(self, B, c0, c1, mult=SKIP, count=SKIP)[0]
+
+    def _found_in(self, B, c0, c1, lo, hi):
+        """the rows of self whose find_in(B) lies in [lo, hi] (the selection's compare is signed), in their order, as a new DMat"""
+        idx = self.find_in(B, c0, c1)
+        kptr, own_k = _out(None, self.nrows, always=True)
+        n = select_weights(idx.ptr, self.nrows, lo, hi, idx=kptr, cap=self.nrows)[1]
+        D = DMat(n, self.ncols)
+        return gather_rows(self, kptr, D=D)[0] if n else D
+
+    def difference(self, B, c0=0, c1=None):
+        """The rows of self that equal no row of B on the columns [c0, c1) (None: as in find_in), in the order they had, as a new DMat
+        (include/m4ri_hip_find.h).  The count of those rows is read back once, to size the result."""
+        return self._found_in(B, c0, c1, -1, -1)
+
+    def intersection(self, B, c0=0, c1=None):
+        """The rows of self that equal a row of B on the columns [c0, c1) (None: as in find_in), in the order they had, as a new DMat
+        (include/m4ri_hip_find.h).  The count of those rows is read back once, to size the result."""
+        return self._found_in(B, c0, c1, 0, 2**31 - 1)
+
     def subset_sums(self, p, base=None):
         """All C(nrows, p) XORs of p rows of self (each ^ base, a 1-row DMat, if given) as a new DMat, in the colexicographic order of
         the subsets: row C(c_1, 1) + ... + C(c_p, p) is the sum of the rows c_1 < ... < c_p (include/m4ri_hip_sums.h)."""
@@ -897,6 +921,30 @@ def unique_rows(P, c0=0, c1=None, keep=None, cap=None, count=None, rep=None, str
     call(kptr, cap, rptr)
     _used(stream, own_k, own_c, own_r)
     return own_k, own_c, own_r
+
+
+def find_rows_plan(nrows_a, nrows_b, ncols, c0=0, c1=None):
+    """How the lookup of nrows_a rows among nrows_b rows on the columns [c0, c1) (c1 = None: to the last column) runs
+    (include/m4ri_hip_find.h, no device needed) -> (slots of the table, capped at 2^31 - 1, slots, bytes per slot, scratch bytes,
+    launches, rows per workgroup of the build kernel, of the lookup kernel, the form (0: a lane per row, 1: a wave per row), words of a
+    row in the range); None for a bad shape or range."""
+    return _plan(_lib.lib().gf2_find_rows_plan, (nrows_a, nrows_b, ncols) + _crange(ncols, c0, c1), 8)
+
+
+def find_rows(A, B, c0=0, c1=None, idx=None, mult=None, count=None, stream=None):
+    """Every row of A looked up among the rows of B on the columns [c0, c1) (c1 = None: to the last column of the narrower of the two;
+    include/m4ri_hip_find.h) -> (idx, mult, count): idx[i] the lowest row of B equal to row i of A, -1 for none; mult[i] how many rows
+    of B are equal to it; A.nrows int32 each; `count` (one int32) the rows of A that were found.  mult and count may be SKIP.  A may
+    be B: idx is then the rep of unique_rows and mult the class sizes.  Only enqueues; the objects are always there.  idx cannot be
+    skipped (ValueError): with neither idx nor mult wanted there is nothing to look up."""
+    if idx is not None and idx == SKIP:
+        raise ValueError("find_rows: idx cannot be SKIP (mult and count can)")
+    c0, c1 = _crange(min(A.ncols, B.ncols), c0, c1)
+    ptrs, owned = _outs((idx, mult), A.nrows, always=True)
+    cptr, own_c = _out(count, 1)
+    _lib.check(_lib.lib().gf2_find_rows_dev(A._on(stream), B._on(stream), c0, c1, ptrs[0], ptrs[1], cptr, stream), "gf2_find_rows_dev")
+    _used(stream, own_c, *owned)
+    return owned[0], owned[1], own_c
 
 
 def subset_count(n, p):
