@@ -313,6 +313,15 @@ _TABLES["m4ri_hip_find.h"] = {
 }
 FIND_SYMBOLS = tuple(_TABLES["m4ri_hip_find.h"])
 
+# ... and include/m4ri_hip_join_rows.h (tests/test_join_rows_contract.py)
+_TABLES["m4ri_hip_join_rows.h"] = {
+    "gf2_group_rows_dev": (_I, [DMatP, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gf2_join_rows_dev": (_I, [DMatP, DMatP, DMatP, _I, _I, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _I, _I,
+                               ctypes.c_void_p]),
+    "gf2_join_rows_plan": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_longlong)]),
+}
+JOIN_ROWS_SYMBOLS = tuple(_TABLES["m4ri_hip_join_rows.h"])
+
 _lib = None
 
 

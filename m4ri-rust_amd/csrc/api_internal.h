@@ -62,6 +62,7 @@ enum Gf2ScratchSlot {
   GF2_SLOT_NEAR = 16,                  // near/near_host.cpp: the cells (row of A, chunk of B) of gf2_near_pairs_dev and gf2_nearest_dev
   GF2_SLOT_UNIQUE = 17,                // unique/unique_host.cpp: the sort's work space, run carries, sorted order and block counts of gf2_sort_rows_dev / gf2_unique_rows_dev
   GF2_SLOT_FIND = 18,                  // find/find_host.cpp: the hash table (entries, member counts) of gf2_find_rows_dev
+  GF2_SLOT_JOIN_ROWS = 19,             // join_rows/join_rows_host.cpp: the table over B, rep, class starts, the sort's work space, sorted order, idx, mult, offsets and run sums of gf2_group_rows_dev / gf2_join_rows_dev
 };
 int gf2_stream_scratch(hipStream_t s, size_t bytes, void **out, int slot);  // slot: a Gf2ScratchSlot
 // counts a run of a host routine of the size dispatch (gf2_host_small_calls)

@@ -267,6 +267,20 @@ class DMat:
         (include/m4ri_hip_find.h).  The count of those rows is read back once, to size the result."""
         return self._found_in(B, c0, c1, 0, 2**31 - 1)
 
+    def group_rows(self, c0=0, c1=None):
+        """The rows of self grouped by their columns [c0, c1) (None: to the last column): the rows of a class together and ascending,
+        the classes by their lowest row, as the device array of the row at every position (.ptr feeds gather_rows, .read(stream)
+        gives numpy; include/m4ri_hip_join_rows.h)."""
+        return group_rows(self, c0, c1, head=SKIP)[0]
+
+    def join_rows(self, other, c0=0, c1=None, wcols=None):
+        """The join with another pool on a column range of any width as a new DMat of exactly `count` rows: the XOR of every pair of a
+        row of self and a row of `other` that are equal on the columns [c0, c1) (None: to the last column), ordered by (row of self,
+        row of other) (include/m4ri_hip_join_rows.h).  With wcols = (wc0, wc1) -> (D, wt): wt the ones of every row of D in those
+        columns, on the device (.ptr feeds select_weights, .read(stream) gives numpy)."""
+        out = join_rows(self, other, c0, c1, ia=SKIP, ib=SKIP, wt=SKIP if wcols is None else None, wcols=wcols)
+        return out[0] if wcols is None else (out[0], out[4])
+
     def subset_sums(self, p, base=None):
         """All C(nrows, p) XORs of p rows of self (each ^ base, a 1-row DMat, if given) as a new DMat, in the colexicographic order of
         the subsets: row C(c_1, 1) + ... + C(c_p, p) is the sum of the rows c_1 < ... < c_p (include/m4ri_hip_sums.h)."""
@@ -945,6 +959,55 @@ def find_rows(A, B, c0=0, c1=None, idx=None, mult=None, count=None, stream=None)
     _lib.check(_lib.lib().gf2_find_rows_dev(A._on(stream), B._on(stream), c0, c1, ptrs[0], ptrs[1], cptr, stream), "gf2_find_rows_dev")
     _used(stream, own_c, *owned)
     return owned[0], owned[1], own_c
+
+
+def join_rows_plan(nrows_a, nrows_b, ncols, c0=0, c1=None):
+    """How the grouping of nrows_b rows by class and the join of nrows_a with nrows_b rows on the columns [c0, c1) (c1 = None: to the
+    last column) run (include/m4ri_hip_join_rows.h, no device needed) -> (radix passes of the grouping, slots of the table over B, the
+    form of its kernels (0: a lane per row, 1: a wave per row), launches of group_rows without head, launches of join_rows with a
+    capacity, rows of A per workgroup of the sum and offset kernels, outputs per workgroup of the scatter, scratch bytes of
+    group_rows, scratch bytes of join_rows); None for a bad shape or range."""
+    return _plan(_lib.lib().gf2_join_rows_plan, (nrows_a, nrows_b, ncols) + _crange(ncols, c0, c1), 8)
+
+
+def group_rows(P, c0=0, c1=None, order=None, head=None, stream=None):
+    """The rows of P grouped by their columns [c0, c1) (c1 = None: to the last column) without sorting by value
+    (include/m4ri_hip_join_rows.h) -> (order, head): order[s] the rows ascending by (lowest equal row, row) -- the rows of a class
+    together and ascending, the classes by their lowest row --, head[s] the first sorted position of the class of s, P.nrows int32
+    each; head may be SKIP.  Only enqueues; the objects are always there (an address even where no row is grouped)."""
+    c0, c1 = _crange(P.ncols, c0, c1)
+    ptrs, owned = _outs((order, head), P.nrows, always=True)
+    _lib.check(_lib.lib().gf2_group_rows_dev(P._on(stream), c0, c1, ptrs[0], ptrs[1], stream), "gf2_group_rows_dev")
+    _used(stream, *owned)
+    return tuple(owned)
+
+
+def join_rows(A, B, c0=0, c1=None, D=None, cap=None, store=True, count=None, ia=None, ib=None, wt=None, wcols=None, stream=None):
+    """The join of two pools on a column range of any width (include/m4ri_hip_join_rows.h): every pair of a row of A and a row of B
+    that are equal on the columns [c0, c1) (c1 = None: to the last column) is XORed.  -> (D, count, ia, ib, wt): D holds the pairs
+    ordered by (row of A, row of B); `count` (one int64) says how many there are in all, which may exceed the capacity; ia[t] and
+    ib[t] are the rows of A and B that D[t] came from, wt[t] the ones of D[t] in the columns wcols = (wc0, wc1) (None: all columns)
+    (D.nrows int32 each; may be SKIP; they feed gather_rows / select_weights as they are).  Only enqueues; count first, by `count`;
+    store=False: the rows are not stored (D is None in the result).  A may be B: all ordered pairs of a class, (i, i) included."""
+    L = _lib.lib()
+    c0, c1 = _crange(A.ncols, c0, c1)
+    wc0, wc1 = _wcols(A.ncols, wcols)
+    cptr, own_c = _out(count, 1, dtype=np.int64)
+
+    def call(Dm, pa, pb, pw):
+        rc = L.gf2_join_rows_dev(Dm._on(stream), A._on(stream), B._on(stream), c0, c1, cptr, pa, pb, pw, wc0, wc1, stream)
+        _lib.check(rc, "gf2_join_rows_dev")
+
+    if D is not None and not store:
+        raise ValueError("join_rows: store=False takes no D")
+    if D is None:
+        if cap is None:
+            cap = _count_first("join_rows", "pairs", own_c, lambda: call(DMat.wrap(None, 0, A.ncols, A.ld), None, None, None), stream)
+        D = DMat(cap, A.ncols) if store else _unstored(cap, A.ncols)
+    ptrs, owned = _outs((ia, ib, wt), D.nrows)
+    call(D, *ptrs)
+    _used(stream, own_c, *owned)
+    return (D if store else None, own_c) + tuple(owned)
 
 
 def subset_count(n, p):
